@@ -1,20 +1,25 @@
 #!/usr/bin/env python
 """SVGD steps/sec of the DiBS hot path on MI355X (BASELINE.json metric: d=50, n_particles=128, BGe).
 
-    python bench.py --gpus N --steps K --warmup W [--config headline|2|3|4|5]
+    python bench.py --gpus N --steps K --warmup W [--config headline|2|3|4|5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     (N > 1 without a launcher: spawns the N ranks itself)
 
 One "step" = one SVGD step (svgd.py:226-267 / 673-721 of the reference) over all particles on synthetic data that is resident in HBM
 before the timed region.  W untimed steps t = 0..W-1 of the trajectory from PRNGKey(1), then EXACTLY K steps t = W..W+K-1 timed
-between barrier + synchronize fences (max over ranks).  The cost of a step depends on t (sampled parent sets shrink as the particles
-sharpen), so the timed window is restored from a snapshot and measured repeatedly -- at least `--reps` times and until the timed
-regions add up to `--min-seconds` of GPU time: `value` comes from the MEDIAN repetition, `rep_ms_per_step` summarises all of them.
+between barrier + synchronize fences (max over ranks).  A plain run times that window once and prints the line: `value` = K / its
+seconds, `ms_per_step` = its milliseconds / K.  --full adds everything else the benchmark measures: the cost of a step depends on t
+(sampled parent sets shrink as the particles sharpen), so the timed window is restored from a snapshot and measured repeatedly -- at
+least `--reps` (7) times and until the timed regions add up to `--min-seconds` (8) of GPU time: `value` comes from the MEDIAN
+repetition, `rep_ms_per_step` summarises all of them -- plus `steady_state`, the roofline of the dominant kernel with per-kernel timers,
+the CPU baseline and, for N > 1, the per-rank diagnostics and config 4.
+--dump-outputs DIR writes the state after the last timed step (what Engine.get_state() hands a caller) as DIR/<name>.npy (see
+dump_outputs); the inputs depend on the arguments only, so two builds can be compared array for array.
 N > 1 shards the particles over the ranks (strong scaling: total work fixed) and runs the step loop inside the engine
 (dibs_engine_run_sharded): one all-gather of the packed rows per step below 512 particles, from there on the gradient rows between the
 phases and the new values beside the next phase A.  RCCL by default; DIBS_COMM=ipc exchanges through mapped peer memory, so that the
 ranks may share devices (`--gpus 4` on a one-GPU box runs the whole N > 1 path; its value measures processes time-sharing a GPU).
-`steady_state` repeats the timed window from step --steady-t (300) of the same trajectory.
+`steady_state` (--full) repeats the timed window from step --steady-t (300) of the same trajectory.
 Rank 0 prints ONE JSON line (DESIGN.md "Measurement" explains every field).
 
 --config selects the workload: `headline` (default) is BASELINE.json's metric config; 2 .. 5 are BASELINE.json configs[1..4] at their
@@ -37,6 +42,7 @@ PEAK_BF16_TFLOPS = 2500.0  # dense bf16 MFMA peak (MI355X_MICROARCH.md)
 PEAK_HBM_GBPS = 8000.0
 N_SIMD, CLK_GHZ = 1024, 2.4
 VALU_CYC_PER_INSTR = 4.0  # measured issue rate of plain (unpacked) VALU wave-instructions, scripts/probe/valu_rate.hip
+DUMP_BYTES = 64 << 20     # --dump-outputs: at most this much in all
 
 CONFIGS = {
     "headline": dict(d=50, M=128, model="bge", label="MarginalDiBS+BGe (score-function estimator), Erdos-Renyi-2 linear-Gaussian data"),
@@ -45,6 +51,21 @@ CONFIGS = {
     "4": dict(d=50, M=1024, model="bge", label="BASELINE configs[3]: BGe, d=50, 1024 particles (MarginalDiBS: JointDiBS+BGe is not constructible)"),
     "5": dict(d=100, M=256, model="densenn", label="BASELINE configs[4]: JointDiBS+DenseNonlinearGaussian (5,), d=100, 256 particles, interv_mask, scale-free prior"),
 }
+
+
+def dump_outputs(path, state):
+    """One .npy per array of `state`: float arrays as float32, the PRNG key as float64 (exact).  If they would exceed DUMP_BYTES in all,
+    every array above an equal share of it is cut to that many elements of its flattened form, chosen by np.random.default_rng(0) and
+    kept in order: the same elements for the same shapes, whichever build wrote them."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: np.asarray(v, np.float64 if v.dtype.kind in "iu" else np.float32) for k, v in state.items() if v is not None}
+    share = None
+    if sum(a.nbytes for a in arrs.values()) > DUMP_BYTES:
+        share = DUMP_BYTES // 8 // len(arrs)   # elements (8 bytes bounds both dtypes)
+    for k, a in arrs.items():
+        if share is not None and a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(path, f"{k}.npy"), a)
 
 
 def binary_powering_matmuls(n):
@@ -181,17 +202,26 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="headline", choices=list(CONFIGS))
-    ap.add_argument("--reps", type=int, default=7, help="minimum repetitions of the timed window (median reported)")
-    ap.add_argument("--min-seconds", type=float, default=8.0, help="repeat the timed window until the timed regions add up to this much")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline window: its repetitions (median reported), steady_state, roofline and per-kernel timers, the CPU "
+                         "baseline, the sharded diagnostics")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the state after the last timed step to DIR/<name>.npy")
+    ap.add_argument("--reps", type=int, default=None, help="minimum repetitions of the timed window (median reported; default 7 with --full, else 1)")
+    ap.add_argument("--min-seconds", type=float, default=None,
+                    help="repeat the timed window until the timed regions add up to this much (default 8 with --full, else 0)")
     ap.add_argument("--n-particles", type=int, default=None, help="override the particle count of the config")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--steady-t", type=int, default=300,
-                    help="also time the same K-step window from this step of the trajectory (sample() runs thousands of steps: the sampled parent "
+                    help="with --full: also time the same K-step window from this step of the trajectory (sample() runs thousands of steps: the sampled parent "
                          "sets shrink as the particles sharpen and a step gets cheaper); 0: skip.  Reported as `steady_state`, never as `value`")
     ap.add_argument("--dist-smoke", action="store_true",
                     help="with --gpus 1: run the sharded code path (process group of ONE rank, real RCCL calls, overlapped exchange) instead of "
                          "dibs_engine_run -- exercises on one GPU what --gpus N > 1 executes")
     args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 7 if args.full else 1
+    if args.min_seconds is None:
+        args.min_seconds = 8.0 if args.full else 0.0
     K, W, N = args.steps, args.warmup, args.gpus
     M = args.n_particles or CONFIGS[args.config]["M"]
     if args.config == "headline" and M == 1024:
@@ -349,6 +379,14 @@ def main():
         return eng, run, snap, rep_s, (cfg, x, mask), (tstream, send, recv, restore)
 
     eng, run, snap, rep_s, (cfg, x, mask), (tstream, send, recv, restore) = measure(args.config, M, args.reps, args.min_seconds)
+    if args.dump_outputs:
+        state = eng.get_state()   # t = W + K (every repetition starts from the snapshot at t = W)
+        if dist is not None:      # this rank's particles: rank 0 writes them all, in rank order (the key is the same on every rank)
+            parts = [None] * N
+            dist.all_gather_object(parts, state)
+            state = {k_: v if k_ == "key" or v is None else np.concatenate([p[k_] for p in parts]) for k_, v in state.items()}
+        if rank == 0:
+            dump_outputs(args.dump_outputs, state)
     elapsed = float(np.median(rep_s))
     steps_per_s = K / elapsed
     c = CONFIGS[args.config]
@@ -374,7 +412,7 @@ def main():
     if loop_note:
         out["config"]["parallelism"] = f"particles sharded over {N} rank(s), step loop driven from Python, collectives by " + loop_note["loop"]
 
-    if sharded:
+    if sharded and args.full:
         # ---- diagnosis of a sharded run: per-rank kernel timers, the collective alone, config 4 beside the strong-scaling headline ----
         restore(snap)
         eng.set_profiling(True)
@@ -416,7 +454,7 @@ def main():
                               "n_gpus": N, "particles_per_rank": 1024 // N, "scaling": "weak vs the 1-GPU headline (128 particles per rank at 8 GPUs)"}
             eng = e4
 
-    if not sharded and args.steady_t > W + K:
+    if args.full and not sharded and args.steady_t > W + K:
         # ---- the same K-step window late in the trajectory (untimed run-up from the snapshot at t = W, then the window repeated from a snapshot)
         eng.set_state(**snap)
         eng.run(W, args.steady_t - W)
@@ -433,7 +471,7 @@ def main():
         out["steady_state"] = {"value": K / el_late, "unit": "steps/s", "ms_per_step": 1e3 * el_late / K, "reps": len(late),
                                "timed_steps": f"t={args.steady_t}..{args.steady_t + K - 1} of the same trajectory"}
 
-    if rank == 0 and not sharded:
+    if args.full and rank == 0 and not sharded:
         # ---- roofline of the dominant kernel: the same K steps replayed with per-kernel HIP events on the engine's stream ----
         eng.set_state(**snap)
         eng.set_profiling(True)
@@ -481,7 +519,9 @@ def main():
             # ---- CPU baseline: the oracle's C port on this box's host cores, bounded sample of the SAME window (from t = W) ----
             from oracle.c_oracle import COracle
             from dibs_amd._abi import DibsConfig
-            cores = min(os.cpu_count() or 1, M)   # OpenMP THREADS used (os.cpu_count() counts hardware threads, not physical cores); over particles: more threads than particles are idle
+            # OpenMP THREADS used: OMP_NUM_THREADS where the host sets it (a share of a larger machine), else os.cpu_count() (hardware
+            # threads, not physical cores); over particles: more threads than particles are idle
+            cores = min(int(os.environ.get("OMP_NUM_THREADS", "0") or 0) or os.cpu_count() or 1, M)
             cfg1 = DibsConfig.from_buffer_copy(cfg)
 
             def cpu(prec, n_steps, mode):
@@ -498,7 +538,7 @@ def main():
             out["cpu_baseline"] = {"value": faithful, "unit": "steps/s", "cores": cores, "kind": "port",
                                    "sample": f"{n_cpu} steps (t={W}..{W + n_cpu - 1}) of the same workload from the same state, f32 C port of the "
                                              "reference algorithm" + (" (masked d x d LU slogdet per node, func.py:128-145)" if c["model"] == "bge" else "")
-                                             + f", OpenMP over particles on {cores} threads (hardware threads of the host, not physical cores)", "threads": cores}
+                                             + f", OpenMP over particles on {cores} threads", "threads": cores}
             if c["model"] == "bge":
                 out["cpu_baseline_compact_f32"] = {"value": cpu("f32", n_cpu, 1), "unit": "steps/s", "cores": cores, "kind": "port",
                                                    "sample": f"{n_cpu} steps, same port with the GPU's compact parent-set Cholesky"}

@@ -439,7 +439,7 @@ def test_bench_sharded_path_on_one_gpu():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--dist-smoke", "--steps", "4", "--warmup", "3", "--reps", "2",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--dist-smoke", "--full", "--steps", "4", "--warmup", "3", "--reps", "2",
                         "--min-seconds", "0", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -457,3 +457,33 @@ def test_bench_sharded_path_on_one_gpu():
     assert r.returncode == 0, r.stderr[-2000:]
     out2 = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert out2["value"] > 100 and "torch.distributed" in out2["config"]["parallelism"]
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run times exactly --steps steps once, prints the headline fields only, and with --dump-outputs writes the state
+    after its last timed step: the same state an engine reaches on the same inputs (W untimed steps, then K), array for array."""
+    import subprocess
+    import sys
+    from dibs_amd import random
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    W, K = 3, 4
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W),
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == K and out["warmup"] == W and out["reps"] == 1 and out["higher_is_better"] and out["dtype"] == "f32"
+    assert out["value"] > 100 and abs(out["ms_per_step"] * out["value"] - 1e3) < 1e-6 * 1e3
+    assert not {"steady_state", "roofline", "cpu_baseline", "kernel_us_per_step"} & set(out)
+    import bench
+    cfg, x, _ = bench.make_workload("headline", 128)
+    eng = _engine(cfg, x)
+    eng.init_particles(random.PRNGKey(1))
+    eng.run(0, W)
+    eng.run(W, K)
+    st = eng.get_state()
+    eng.close()
+    assert sorted(os.listdir(tmp_path)) == ["baseline.npy", "key.npy", "v_z.npy", "z.npy"]
+    for k_ in ("z", "v_z", "baseline"):
+        a = np.load(tmp_path / f"{k_}.npy")
+        assert a.dtype == np.float32 and a.shape == st[k_].shape and rel_err(a, st[k_]) < 1e-6, k_
+    assert np.array_equal(np.load(tmp_path / "key.npy"), st["key"].astype(np.float64))
