@@ -66,6 +66,18 @@ struct dibs_engine {
   dibs_config cfg;
   DibsTuning tune;  // the environment switches (tuning.h), latched at creation
   int d, k, M, Mloc, m0, N, S, Sa, W;
+  // batched engine (cfg.reserved_i[0] = n_problems = B > 1): B independent problems of M particles each; the device arrays hold Mloc = B * M
+  // rows, problem-major (m0 = 0).  M stays the size of ONE problem, so every choice the standalone engine makes from its particle count
+  // (acyclicity chain grouping, kernel-matrix algorithm) is made the same way here.  See step_batch.
+  int B = 1;
+  Key2* bcarry = nullptr;                             // [B] loop-carry keys, advanced on the device (k_batch_keys)
+  Key2 *bkeys_lik = nullptr, *bkeys_prior = nullptr;  // [B * M] this step's per-particle keys
+  struct BatchStats {                                 // host copies of the stacked BGe statistics (padded to d matrices per problem)
+    std::vector<float> Rp, Qp;
+    std::vector<double> gam, Nj, ldR;
+    std::vector<char> set;
+    double alpha_lambd = 0;
+  } bst;
   int64_t D, P, E, Ev;  // z elems / theta elems per particle, packed row stride [z | grad_z | theta | grad_theta], plane row stride [z | theta] (floats)
   int dpad, ldk, edge_kc, acyc_nt, acyc_cpb, acyc_nblk, acyc_units;
   float sigz;
@@ -214,9 +226,10 @@ static int engine_alloc(dibs_engine* e, const dibs_config& c, void* stream) {
   e->tune = dibs_tuning_from_env();
   e->d = c.n_vars;
   e->k = c.n_dim;
+  e->B = c.reserved_i[0] > 1 ? c.reserved_i[0] : 1;
   e->M = c.n_particles;
-  e->Mloc = c.n_particles / c.n_ranks;
-  e->m0 = c.rank * e->Mloc;
+  e->Mloc = e->B > 1 ? e->B * c.n_particles : c.n_particles / c.n_ranks;
+  e->m0 = c.rank * (c.n_particles / c.n_ranks);
   e->N = c.n_observations;
   e->S = c.n_grad_mc_samples;
   e->Sa = c.n_acyclicity_mc_samples;
@@ -346,13 +359,18 @@ static int engine_alloc(dibs_engine* e, const dibs_config& c, void* stream) {
   }
   HIP_OK(dalloc(&e->logprobs_z, Ml * e->S));
   HIP_OK(dalloc(&e->logprobs_th, Ml * e->S));
-  HIP_OK(dalloc(&e->pack, (size_t)e->M * e->E));
+  HIP_OK(dalloc(&e->pack, (size_t)(e->B > 1 ? e->Mloc : e->M) * e->E));
+  if (e->B > 1) {
+    HIP_OK(dalloc(&e->bcarry, (size_t)e->B));
+    HIP_OK(dalloc(&e->bkeys_lik, (size_t)e->Mloc));
+    HIP_OK(dalloc(&e->bkeys_prior, (size_t)e->Mloc));
+  }
   // (k_phi_gemm reads whole 128-row x 32-column tiles without bounds checks: rows padded to a multiple of 128, one more tile row of slack)
   const size_t kpad = (((Ml + 127) / 128) * 128 - Ml) * e->M + 64;
   HIP_OK(dalloc(&e->kz, Ml * e->M + kpad));
   if (c.joint) HIP_OK(dalloc(&e->kt, Ml * e->M + kpad));
   if (c.joint) HIP_OK(dalloc(&e->ksum, Ml * e->M + kpad));
-  if (e->M >= e->tune.kmat_tiled_min) {  // (the same rule on every rank: it depends on the global particle count only)
+  if (e->M >= e->tune.kmat_tiled_min && e->B == 1) {  // (the same rule on every rank: it depends on the global particle count only)
     // room for up to 32 pieces per pair, less for many particles (<= 512 MiB); 1 = no buffer, every unit holds whole distances
     size_t ns = ((size_t)512 << 20) / (Ml * e->M * 8);
     ns = ns > 32 ? 32 : (ns < 1 ? 1 : ns);
@@ -411,6 +429,29 @@ extern "C" int dibs_engine_create(const dibs_config* cfg, void* stream, dibs_eng
   if (c.n_particles < 1 || c.n_grad_mc_samples < 1 || c.n_acyclicity_mc_samples < 1) return fail("sizes must be >= 1");
   if (c.n_ranks < 1 || c.rank < 0 || c.rank >= c.n_ranks) return fail("bad rank / n_ranks");
   if (c.n_particles % c.n_ranks) return fail("n_particles must be divisible by n_ranks");
+  {
+    // batched engine (n_problems > 1, include/dibs_hip.h): MarginalDiBS + BGe + score estimator on one rank
+    const int64_t B = c.reserved_i[0];
+    if (B < 0) return fail("n_problems (reserved_i[0]) must be >= 0");
+    if (B > 1) {
+      if (c.joint) return fail("batched engine (n_problems > 1): joint models are not supported (MarginalDiBS + BGe only)");
+      if (c.likelihood != DIBS_LIK_BGE) return fail("batched engine (n_problems > 1): only the BGe marginal likelihood is supported");
+      if (c.grad_estimator_z != DIBS_EST_SCORE)
+        return fail("batched engine (n_problems > 1): the reparam estimator is not supported (score-function estimator only)");
+      if (c.n_ranks != 1) return fail("batched engine (n_problems > 1): n_ranks must be 1 (a batch is not sharded over ranks)");
+      const DibsTuning tn = dibs_tuning_from_env();
+      if (c.n_particles >= 256 || c.n_particles >= tn.kmat_t64_min)
+        return fail("batched engine (n_problems > 1): n_particles (per problem) must be < 256");
+      const int64_t d = c.n_vars, rows = B * c.n_particles;
+      // queue code (m d + j) S + s of k_bge_sample / k_bge_chol is 32-bit, and so is every queue's capacity (rows d S entries)
+      if (rows * d * c.n_grad_mc_samples >= ((int64_t)1 << 32))
+        return fail("batched engine (n_problems > 1): n_problems * n_particles * n_vars * n_grad_mc_samples must be < 2^32");
+      // k_bge_chol addresses the stacked matrices [B d][2][d + 1][d + 1] with 32-bit float offsets
+      if (d <= 128 && 2 * B * d * (d + 1) * (d + 1) >= ((int64_t)1 << 31))
+        return fail("batched engine (n_problems > 1): n_problems * n_vars * (n_vars + 1)^2 too large for the factorisation kernel");
+      if (rows > ((int64_t)1 << 24)) return fail("batched engine (n_problems > 1): n_problems * n_particles too large");
+    }
+  }
   if (c.grad_estimator_z != DIBS_EST_SCORE && c.grad_estimator_z != DIBS_EST_REPARAM)
     return fail("Unknown gradient estimator");  // dibs.py:318 (ValueError)
   if (c.optimizer != DIBS_OPT_GD && c.optimizer != DIBS_OPT_RMSPROP) return fail("unknown optimizer");  // svgd.py:122
@@ -480,7 +521,7 @@ extern "C" int dibs_engine_destroy(dibs_engine* e) {
   if (e->stream2) hipStreamSynchronize(e->stream2);
   void* ptrs[] = {e->z, e->vz, e->theta, e->vtheta, e->baseline, e->baseline2, e->scores, e->probs, e->eas, e->thr, e->w_lik, e->acyc_part, e->w_acyc,
                   e->logprobs_z, e->logprobs_th, e->pack, e->kz, e->kt, e->phi_z, e->phi_th, e->counters, e->masks,
-                  e->node_scores, e->x, e->mask, e->bq.list, e->bq.counts, e->soft_ds, e->acyc_big, e->w_tot, e->join_flag, e->fork_flag, e->carry_bak, e->soft_tri, e->ksum, e->kpart, e->kmat_ctr};
+                  e->node_scores, e->x, e->mask, e->bq.list, e->bq.counts, e->soft_ds, e->acyc_big, e->w_tot, e->join_flag, e->fork_flag, e->carry_bak, e->soft_tri, e->ksum, e->kpart, e->kmat_ctr, e->bcarry, e->bkeys_lik, e->bkeys_prior};
   for (void* p : ptrs)
     if (p) hipFree(p);
   joint_free(&e->jw);
@@ -537,9 +578,15 @@ static bool spd_inverse_logdet(std::vector<double>& a, int n, double* logdet) {
   return true;
 }
 
-static int bge_prepare(BgeStats* st, const dibs_config& cfg, int d, int N, const float* x, const int32_t* mask, const float* mean_obs) {
+// the host part of bge_prepare: the statistics of one data set (n_mats = 1 without interventions, d with)
+struct BgeHost {
+  int n_mats = 1;
+  double alpha_lambd = 0, alpha_mu = 0, log_t = 0;
+  std::vector<float> R, Rp, Qp;
+  std::vector<double> Nj, gam, ldR;
+};
+static int bge_host_stats(BgeHost* st, const dibs_config& cfg, int d, int N, const float* x, const int32_t* mask, const float* mean_obs) {
   const double amu = cfg.bge_alpha_mu;
-  st->release();
   st->alpha_lambd = cfg.bge_alpha_lambd > 0 ? cfg.bge_alpha_lambd : d + 2.0;
   if (!(st->alpha_lambd > d + 1)) return fail("BGe: alpha_lambd must be > n_vars + 1");  // linearGaussian.py:47
   const double small_t = amu * (st->alpha_lambd - d - 1) / (amu + 1);
@@ -550,8 +597,19 @@ static int bge_prepare(BgeStats* st, const dibs_config& cfg, int d, int N, const
     for (int64_t i = 0; i < (int64_t)N * d; ++i) any |= mask[i] != 0;
   st->n_mats = any ? d : 1;
   const int n_mats = st->n_mats, dp = d + 1;
-  std::vector<float> R((size_t)n_mats * d * d), Rp((size_t)n_mats * dp * dp, 0.f), Qp((size_t)n_mats * dp * dp, 0.f);
-  std::vector<double> Nj(d), gam((size_t)d * (d + 1)), xb(d), ldR(n_mats), Rd((size_t)d * d);
+  std::vector<float>& R = st->R;
+  std::vector<float>& Rp = st->Rp;
+  std::vector<float>& Qp = st->Qp;
+  std::vector<double>& Nj = st->Nj;
+  std::vector<double>& gam = st->gam;
+  std::vector<double>& ldR = st->ldR;
+  R.assign((size_t)n_mats * d * d, 0.f);
+  Rp.assign((size_t)n_mats * dp * dp, 0.f);
+  Qp.assign((size_t)n_mats * dp * dp, 0.f);
+  Nj.assign(d, 0.0);
+  gam.assign((size_t)d * (d + 1), 0.0);
+  ldR.assign(n_mats, 0.0);
+  std::vector<double> xb(d), Rd((size_t)d * d);
   for (int jm = 0; jm < n_mats; ++jm) {
     double Nn = 0;
     for (int n = 0; n < N; ++n) Nn += (any && mask[(int64_t)n * d + jm]) ? 0.0 : 1.0;
@@ -587,6 +645,19 @@ static int bge_prepare(BgeStats* st, const dibs_config& cfg, int d, int N, const
                                      lgamma(0.5 * (al - d + l + 1)) - 0.5 * Nn * log(M_PI) +
                                      0.5 * (al - d + 2 * l + 1) * log(small_t);
     }
+  return 0;
+}
+
+static int bge_prepare(BgeStats* st, const dibs_config& cfg, int d, int N, const float* x, const int32_t* mask, const float* mean_obs) {
+  st->release();
+  BgeHost h;
+  if (bge_host_stats(&h, cfg, d, N, x, mask, mean_obs)) return 1;
+  st->alpha_lambd = h.alpha_lambd;
+  st->alpha_mu = h.alpha_mu;
+  st->log_t = h.log_t;
+  st->n_mats = h.n_mats;
+  const std::vector<float> &R = h.R, &Rp = h.Rp, &Qp = h.Qp;
+  const std::vector<double> &Nj = h.Nj, &gam = h.gam, &ldR = h.ldR;
   HIP_OK(dalloc(&st->R, R.size()));
   // R and Q = R^-1 in one allocation: the factorisation kernel addresses a problem's matrix as a 32-bit float offset from Rp, and two
   // separate hipMalloc blocks can lie more than 2^31 floats apart on a 288 GB device (intermittent memory faults with interventions or
@@ -607,6 +678,7 @@ static int bge_prepare(BgeStats* st, const dibs_config& cfg, int d, int N, const
 
 extern "C" int dibs_engine_set_data(dibs_engine* e, const float* x, const int32_t* interv_mask, const float* bge_mean_obs) {
   if (!e || !x) return fail("null argument");
+  if (e->B > 1) return fail("batched engine: use dibs_engine_set_data_problem");
   HIP_OK(hipSetDevice(e->cfg.device_id));
   HIP_OK(hipStreamSynchronize(e->stream));
   e->score_cache.valid = false;  // (the BGe prior mean travels with the data)
@@ -635,6 +707,7 @@ extern "C" int dibs_engine_set_data(dibs_engine* e, const float* x, const int32_
 
 extern "C" int dibs_engine_init_particles(dibs_engine* e, const uint32_t key[2]) {
   if (!e || !key) return fail("null argument");
+  if (e->B > 1) return fail("batched engine: use dibs_engine_init_particles_batch");
   HIP_OK(hipSetDevice(e->cfg.device_id));
   const int L = e->cfg.rng_layout;
   const Key2 k0{key[0], key[1]};
@@ -672,6 +745,7 @@ extern "C" int dibs_engine_init_particles(dibs_engine* e, const uint32_t key[2])
 extern "C" int dibs_engine_set_state(dibs_engine* e, const float* z, const float* v_z, const float* theta,
                                      const float* v_theta, const uint32_t* key, const float* baseline) {
   if (!e) return fail("null engine");
+  if (e->B > 1 && key) return fail("batched engine: the loop-carry keys go through dibs_engine_set_keys (key must be null)");
   HIP_OK(hipSetDevice(e->cfg.device_id));
   HIP_OK(hipStreamSynchronize(e->stream));
   const size_t nz = (size_t)e->Mloc * e->D * 4, nt = (size_t)e->Mloc * e->P * 4;
@@ -690,6 +764,7 @@ extern "C" int dibs_engine_set_state(dibs_engine* e, const float* z, const float
 extern "C" int dibs_engine_get_state(dibs_engine* e, float* z, float* v_z, float* theta, float* v_theta, uint32_t* key,
                                      float* baseline) {
   if (!e) return fail("null engine");
+  if (e->B > 1 && key) return fail("batched engine: the loop-carry keys go through dibs_engine_get_keys (key must be null)");
   HIP_OK(hipSetDevice(e->cfg.device_id));
   HIP_OK(hipStreamSynchronize(e->stream));
   const size_t nz = (size_t)e->Mloc * e->D * 4, nt = (size_t)e->Mloc * e->P * 4;
@@ -702,6 +777,116 @@ extern "C" int dibs_engine_get_state(dibs_engine* e, float* z, float* v_z, float
     key[1] = e->key.b;
   }
   if (baseline) HIP_OK(hipMemcpy(baseline, e->baseline, (size_t)e->Mloc * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ---- batched engine: data, particles and keys per problem (include/dibs_hip.h, n_problems) ----------------------------------------------------
+static int need_batch(const dibs_engine* e) {
+  if (!e) return fail("null engine");
+  if (e->B <= 1) return fail("not a batched engine (dibs_config.reserved_i[0] = n_problems must be > 1)");
+  return 0;
+}
+
+extern "C" int dibs_engine_set_data_problem(dibs_engine* e, int32_t p, const float* x, int32_t n_obs, const int32_t* interv_mask,
+                                            const float* bge_mean_obs) {
+  if (need_batch(e)) return 1;
+  if (!x) return fail("null argument");
+  if (p < 0 || p >= e->B) return fail("problem index out of range");
+  if (n_obs < 1) return fail("n_obs must be >= 1");
+  HIP_OK(hipSetDevice(e->cfg.device_id));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  if (e->stream2) HIP_OK(hipStreamSynchronize(e->stream2));
+  const int d = e->d, dp = d + 1;
+  const size_t msz = (size_t)dp * dp;
+  BgeHost h;
+  if (bge_host_stats(&h, e->cfg, d, n_obs, x, interv_mask, bge_mean_obs)) return 1;
+  dibs_engine::BatchStats& b = e->bst;
+  if (b.set.empty()) {
+    b.Rp.assign((size_t)e->B * d * msz, 0.f);
+    b.Qp.assign((size_t)e->B * d * msz, 0.f);
+    b.gam.assign((size_t)e->B * d * dp, 0.0);
+    b.Nj.assign((size_t)e->B * d, 0.0);
+    b.ldR.assign((size_t)e->B * d, 0.0);
+    b.set.assign((size_t)e->B, 0);
+  }
+  b.alpha_lambd = h.alpha_lambd;
+  // problem p's rows p d .. p d + d - 1: without interventions the one matrix (and logdet) repeated for every node -- the values the
+  // standalone engine reads for every node from its single copy
+  for (int j = 0; j < d; ++j) {
+    const int jm = h.n_mats > 1 ? j : 0;
+    const size_t row = (size_t)p * d + j;
+    memcpy(&b.Rp[row * msz], &h.Rp[(size_t)jm * msz], msz * 4);
+    memcpy(&b.Qp[row * msz], &h.Qp[(size_t)jm * msz], msz * 4);
+    b.ldR[row] = h.ldR[jm];
+    b.Nj[row] = h.Nj[j];
+    memcpy(&b.gam[row * dp], &h.gam[(size_t)j * dp], (size_t)dp * 8);
+  }
+  b.set[p] = 1;
+  e->has_data = false;
+  e->score_cache.valid = false;
+  BgeStats& st = e->bge;
+  if (!st.Rp) {  // the stacked arrays, allocated once ([B d] rows; Rp and Qp in one allocation, see bge_prepare)
+    HIP_OK(dalloc(&st.Rp, 2 * b.Rp.size()));
+    st.Qp = st.Rp + b.Rp.size();
+    HIP_OK(dalloc(&st.gam, b.gam.size()));
+    HIP_OK(dalloc(&st.Nj, b.Nj.size()));
+    HIP_OK(dalloc(&st.ldR, b.ldR.size()));
+    hipDeviceSynchronize();  // (dalloc's zero fills ran on the null stream)
+  }
+  st.alpha_lambd = h.alpha_lambd;
+  st.alpha_mu = h.alpha_mu;
+  st.log_t = h.log_t;
+  st.n_mats = e->B * d;
+  const size_t r0 = (size_t)p * d;
+  HIP_OK(hipMemcpy(st.Rp + r0 * msz, &b.Rp[r0 * msz], (size_t)d * msz * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(st.Qp + r0 * msz, &b.Qp[r0 * msz], (size_t)d * msz * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(st.gam + r0 * dp, &b.gam[r0 * dp], (size_t)d * dp * 8, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(st.Nj + r0, &b.Nj[r0], (size_t)d * 8, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(st.ldR + r0, &b.ldR[r0], (size_t)d * 8, hipMemcpyHostToDevice));
+  bool all = true;
+  for (char f : b.set) all = all && f;
+  e->has_data = all;
+  return 0;
+}
+
+extern "C" int dibs_engine_init_particles_batch(dibs_engine* e, const uint32_t* keys) {
+  if (need_batch(e)) return 1;
+  if (!keys) return fail("null argument");
+  HIP_OK(hipSetDevice(e->cfg.device_id));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  const int L = e->cfg.rng_layout;
+  std::vector<Key2> carry((size_t)e->B);
+  const uint64_t n = (uint64_t)e->M * e->D;
+  for (int p = 0; p < e->B; ++p) {  // per problem exactly dibs_engine_init_particles(keys[p]) of a standalone engine
+    const Key2 k0{keys[2 * p], keys[2 * p + 1]};
+    carry[p] = rng_split_row(k0, 2, 0, L);
+    const Key2 subk = rng_split_row(k0, 2, 1, L);
+    const Key2 isub = rng_split_row(subk, 2, 1, L);
+    hipLaunchKernelGGL(k_init_z, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, e->z + (size_t)p * n, isub, n, (uint64_t)0, n, e->sigz, L);
+  }
+  HIP_OK(hipMemcpyAsync(e->bcarry, carry.data(), carry.size() * sizeof(Key2), hipMemcpyHostToDevice, e->stream));
+  HIP_OK(hipMemsetAsync(e->vz, 0, (size_t)e->Mloc * e->D * 4, e->stream));
+  HIP_OK(hipMemsetAsync(e->baseline, 0, (size_t)e->Mloc * 4, e->stream));
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
+extern "C" int dibs_engine_get_keys(dibs_engine* e, uint32_t* keys) {
+  if (need_batch(e)) return 1;
+  if (!keys) return fail("null argument");
+  HIP_OK(hipSetDevice(e->cfg.device_id));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  HIP_OK(hipMemcpy(keys, e->bcarry, (size_t)e->B * sizeof(Key2), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+extern "C" int dibs_engine_set_keys(dibs_engine* e, const uint32_t* keys) {
+  if (need_batch(e)) return 1;
+  if (!keys) return fail("null argument");
+  HIP_OK(hipSetDevice(e->cfg.device_id));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  HIP_OK(hipMemcpy(e->bcarry, keys, (size_t)e->B * sizeof(Key2), hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -1271,7 +1456,9 @@ __global__ __launch_bounds__(256) void k_copy_segs(CopySegs c) {
 }
 static int carry_copy(dibs_engine* e, bool restore) {
   const size_t nz = (size_t)e->Mloc * e->D, nt = (size_t)e->Mloc * e->P, nb = (size_t)e->Mloc;
-  if (!e->carry_bak) HIP_OK(dalloc(&e->carry_bak, 2 * nz + 2 * nt + nb));
+  // (no zero fill: dalloc's memset runs on the null stream, which the engine's non-blocking stream does not wait for -- it could land after
+  //  the copy below and wipe the backup of the first guarded chunk; every element is written by that copy before it is read)
+  if (!e->carry_bak) HIP_OK(hipMalloc((void**)&e->carry_bak, (2 * nz + 2 * nt + nb) * sizeof(float)));
   float* const b = e->carry_bak;
   float* live[5] = {e->z, e->vz, e->theta, e->vtheta, e->baseline};
   float* bak[5] = {b, b + nz, b + 2 * nz, b + 2 * nz + nt, b + 2 * nz + 2 * nt};
@@ -1301,9 +1488,165 @@ static int run_steps(dibs_engine* e, int t_start, int n_steps) {
   return 0;
 }
 
+// ---- batched engine (n_problems = B > 1, include/dibs_hip.h) -------------------------------------------------------------------------
+// One step of B independent problems in the launches of one standalone step: rows [B * M] problem-major, every per-particle kernel over all
+// rows with explicit keys (Mg = -1, rng_explicit_row) that k_batch_keys derives from the B device-resident carries; the BGe kernels look up
+// problem m / M's statistics (BATCH instantiations); the kernel matrix is block-diagonal [B * M][M] and phi sums over a problem's own block.
+// Fork / join of the second stream by events only (no flags), the kernel matrix standalone on the second stream (no fusions).
+static void kmat_batch(dibs_engine* e, hipStream_t st) {
+  const dibs_config& c = e->cfg;
+  KTimer tm(e, DIBS_K_KMAT, st);
+  // the algorithm of a standalone engine of M particles (kmat_tiled_on): tiled from kmat_tiled_min particles, direct below
+  if (e->M >= e->tune.kmat_tiled_min && kmat_tile_addressable((size_t)2 * e->M, e->E > e->Ev ? e->E : e->Ev, 0, 0)) {
+    const int nta = (e->M + KT_T - 1) / KT_T, tiles = kmat_tile_count(nta, nta, 1), nchunk = kmat_nchunk((int)e->D);
+    const KmatTile kt{e->z, (size_t)e->D, 0, (int)e->D, nullptr, 0, e->M, e->M, nchunk, nta, nta, 1, 1, nchunk, (float)c.scale_latent,
+                      (float)c.h_latent, e->kz, nullptr, nullptr, nullptr};
+    dibs_allow_lds((const void*)k_kmat_tile_batch, kmat_tile_lds_bytes());
+    hipLaunchKernelGGL(k_kmat_tile_batch, dim3((unsigned)tiles, (unsigned)e->B), dim3(KT_NT), kmat_tile_lds_bytes(), st, kt);
+    return;
+  }
+  const size_t lds = (size_t)(((e->D < KMAT_CH ? e->D : (int64_t)KMAT_CH) + 3) & ~(int64_t)3) * 4;
+  allow_lds(k_kmat_batch, lds);
+  hipLaunchKernelGGL(k_kmat_batch, dim3(e->Mloc, (e->M + KMAT_BT - 1) / KMAT_BT), dim3(256), lds, st, (const float*)e->z, (size_t)e->D, (int)e->D,
+                     e->kz, e->M, (float)c.scale_latent, (float)c.h_latent);
+}
+
+static int step_batch(dibs_engine* e, int t) {
+  const dibs_config& c = e->cfg;
+  const float alpha = (float)(c.alpha_linear * t), beta = (float)(c.beta_linear * t);
+  const int L = c.rng_layout, R = e->Mloc;
+  hipLaunchKernelGGL(k_batch_keys, dim3(e->B), dim3(256), 0, e->stream, e->bcarry, e->bkeys_lik, e->bkeys_prior, e->M, L);
+  const Key2 carry_lik = key_array_as_carry(e->bkeys_lik, 0), carry_prior = key_array_as_carry(e->bkeys_prior, 0);
+  {
+    KTimer tm(e, DIBS_K_EDGE);
+    const size_t lds = (size_t)2 * e->dpad * e->ldk * 4;
+    if (e->d <= 64 && e->k <= 64 && e->edge_kc >= e->k && e->ldk <= 128) {
+      allow_lds(k_edge_scores_p, lds);
+      unsigned int* const none = nullptr;
+      hipLaunchKernelGGL(k_edge_scores_p, dim3(R), dim3(1024), lds, e->stream, e->z, e->scores, e->thr, e->probs, e->eas, alpha, e->d, e->k,
+                         e->dpad, e->ldk, none, none, 0u);
+    } else {
+      const int ntile = (e->dpad / 16) * (e->dpad / 16);
+      int nby = ntile >= 16 ? 4 : (ntile >= 8 ? 2 : 1);
+      while (4 * nby * EDGE_MAXT < ntile) nby *= 2;
+      const int per_wave = (ntile + 4 * nby - 1) / (4 * nby);
+      unsigned long long* const none = nullptr;
+#define EDGE_LAUNCH(MAXT_)                                                                                                             \
+      {                                                                                                                                  \
+        allow_lds(k_edge_scores<MAXT_>, lds);                                                                                            \
+        hipLaunchKernelGGL(k_edge_scores<MAXT_>, dim3(R, nby), dim3(256), lds, e->stream, e->z, e->scores, e->thr, e->probs, e->eas,     \
+                           alpha, e->d, e->k, e->dpad, e->ldk, e->edge_kc, none);                                                        \
+      }
+      if (per_wave <= 1) EDGE_LAUNCH(1) else if (per_wave <= 4) EDGE_LAUNCH(4) else EDGE_LAUNCH(EDGE_MAXT)
+#undef EDGE_LAUNCH
+    }
+  }
+  // acyclicity term and kernel matrix on the second stream (both need only this step's z / scores), the likelihood chain on the first
+  const bool fork = e->stream2 != nullptr, join_now = e->profiling && !e->profiling_concurrent;
+  hipStream_t s2 = fork ? e->stream2 : e->stream;
+  if (fork) {
+    HIP_OK(hipEventRecord(e->ev_fork, e->stream));
+    HIP_OK(hipStreamWaitEvent(e->stream2, e->ev_fork, 0));
+  }
+  const AcycLaunch al{s2, e->scores, e->acyc_part, e->w_acyc, e->acyc_big, carry_prior, 0, -1, R, e->d, e->Sa, e->acyc_cpb, e->acyc_units,
+                      e->acyc_nblk, alpha, (float)c.tau, L, c.logistic_minval_tiny, nullptr, nullptr, e->eas, e->tune.acyc_pipe,
+                      e->tune.acyc_hfw_max};
+  acyc_power_timed(e, al, s2);
+  {
+    KTimer tm(e, DIBS_K_ACYC_REDUCE, s2);
+    acyc_launch_reduce(al);
+  }
+  kmat_batch(e, s2);
+  if (fork) {
+    HIP_OK(hipEventRecord(e->ev_join, e->stream2));
+    if (join_now) HIP_OK(hipStreamWaitEvent(e->stream, e->ev_join, 0));
+  }
+  BgeParams bp = e->bge.params();
+  bp.pM = e->M;
+  {
+    KTimer tm(e, DIBS_K_BGE_NODES);
+    bge_launch_sample_batch(e->stream, e->thr, e->masks, e->node_scores, bp, carry_lik, R, e->d, e->S, e->W, L, e->bq);
+  }
+  {
+    KTimer tm(e, DIBS_K_BGE_BIG);
+    bge_launch_chol_batch(e->stream, e->node_scores, bp, e->bq, e->d, e->S);
+  }
+  if (fork && !join_now) HIP_OK(hipStreamWaitEvent(e->stream, e->ev_join, 0));
+  const RowTarget rt = packed_rows(e, e->pack);
+  {
+    KTimer tm(e, DIBS_K_TAIL);
+    float er_c = 0.f;
+    if (c.graph_prior == DIBS_PRIOR_ER) {
+      const double p = c.graph_prior_edges_per_node * e->d / ((e->d * (e->d - 1)) / 2.0);
+      er_c = (float)(log(p) - log(1 - p));
+    }
+    const float inv_sig2 = 1.0f / (e->sigz * e->sigz);
+    const int ldz = e->w_tot ? 0 : tail_ldz(e->d, e->k, e->S, true, LDS_LIMIT - 2048);
+    const int cap = tail_stage_cap(e->d, ldz, e->S, e->W, LDS_LIMIT - 2048);
+    const size_t lds = tail_lds_bytes(e->d, ldz, e->S, e->W, true, cap);
+    const TailArgs ta{e->node_scores, e->masks, e->logprobs_z, e->baseline, e->baseline2, c.score_function_baseline, e->bq.counts, e->S, e->W, cap,
+                      e->probs, e->w_lik, e->w_acyc, alpha, beta, c.graph_prior, er_c, e->z, rt.base, rt.stride, rt.copy_vals, 0, e->d, e->k, ldz,
+                      inv_sig2, nullptr, e->w_tot, nullptr, 0u, e->join_err, R,
+                      KmatTile{nullptr, 0, 0, 0, nullptr, 0, 0, 0, 1, 0, 0, 0, 1, 1, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr}};
+    allow_lds(k_particle_grad, lds);
+    hipLaunchKernelGGL(k_particle_grad, dim3(R), dim3(TAIL_NT), lds, e->stream, ta);
+    if (e->w_tot) {
+      const size_t lb = backproject_big_lds(e->d);
+      allow_lds(k_backproject_big, lb);
+      hipLaunchKernelGGL(k_backproject_big, dim3(R, (e->d + 15) / 16, (e->k + 31) / 32), dim3(256), lb, e->stream, e->w_tot, e->z, rt.base,
+                         rt.stride, rt.copy_vals, 0, e->d, e->k, inv_sig2);
+    }
+    std::swap(e->baseline, e->baseline2);
+  }
+  {
+    // SVGD transform + optimizer step: k_phi_update's BATCH instantiation, grid.y = problem, each problem exactly a standalone launch
+    KTimer tm(e, DIBS_K_PHI_UPDATE);
+    const long cols = (long)((e->D + 63) / 64);
+    int ta = 16;
+    while (ta > 4 && (cols * ((e->M + ta - 1) / ta) < 1024 || phi_update_lds_bytes(ta, e->M) > 56 * 1024)) ta >>= 1;
+    const size_t lds = phi_update_lds_bytes(ta, e->M);
+    const int ngroups = (e->M + ta - 1) / ta;
+    const dim3 g((unsigned)(8 * ngroups * ((cols + 7) / 8)), (unsigned)e->B);
+    const bool full = e->M % 64 == 0 && e->M % ta == 0 && (size_t)e->M * e->E * 4 < ((size_t)1 << 32);
+    float* const none = nullptr;
+#define PHI_LAUNCH(TA_, F_)                                                                                                                 \
+    {                                                                                                                                       \
+      allow_lds(k_phi_update<TA_, F_, false, true>, lds);                                                                                   \
+      hipLaunchKernelGGL((k_phi_update<TA_, F_, false, true>), g, dim3(256), lds, e->stream, (const float*)e->pack, (size_t)e->E, (size_t)0,  \
+                         (size_t)e->D, (int)e->D, (const float*)e->kz, (const float*)nullptr, 0, e->z, e->vz, e->phi_z, 0, e->M, e->M,       \
+                         (float)c.h_latent, (float)c.stepsize, c.optimizer == DIBS_OPT_RMSPROP, (int)cols, ngroups, none, (size_t)0,        \
+                         (size_t)0);                                                                                                         \
+    }
+#define PHI_PICK(TA_) if (full) PHI_LAUNCH(TA_, true) else PHI_LAUNCH(TA_, false)
+    if (ta == 16) { PHI_PICK(16) } else if (ta == 8) { PHI_PICK(8) } else { PHI_PICK(4) }
+#undef PHI_PICK
+#undef PHI_LAUNCH
+  }
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(err));
+  return 0;
+}
+
+static int run_steps_batch(dibs_engine* e, int t_start, int n_steps) {
+  for (int t = t_start; t < t_start + n_steps; ++t) {
+    if (step_batch(e, t)) return 1;
+    if (e->profiling && e->pending.size() > 4096) drain_timers(e);
+  }
+  HIP_OK(hipStreamSynchronize(e->stream));
+  if (e->stream2) HIP_OK(hipStreamSynchronize(e->stream2));
+  if (e->profiling) drain_timers(e);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 extern "C" int dibs_engine_run(dibs_engine* e, int32_t t_start, int32_t n_steps) {
   if (!e) return fail("null engine");
+  if (e->B > 1 && !e->has_data) return fail("dibs_engine_set_data_problem has not been called for every problem");
   if (!e->has_data) return fail("dibs_engine_set_data has not been called");
+  if (e->B > 1) {
+    HIP_OK(hipSetDevice(e->cfg.device_id));
+    return run_steps_batch(e, t_start, n_steps);
+  }
   if (e->cfg.n_ranks != 1) return fail("dibs_engine_run is single-rank; use step_local / step_update");
   HIP_OK(hipSetDevice(e->cfg.device_id));
   latch_flags(e);
@@ -1334,6 +1677,7 @@ extern "C" int dibs_engine_debug_drop_next_flag(dibs_engine* e) {
 
 extern "C" int dibs_engine_step_local(dibs_engine* e, int32_t t, void* send_dev) {
   if (!e || !send_dev) return fail("null argument");
+  if (e->B > 1) return fail("batched engine: only dibs_engine_run steps it");
   if (!e->has_data) return fail("dibs_engine_set_data has not been called");
   HIP_OK(hipSetDevice(e->cfg.device_id));
   latch_flags(e);
@@ -1358,6 +1702,7 @@ extern "C" int dibs_engine_export_values(dibs_engine* e, void* vals_send_dev) {
 
 extern "C" int dibs_engine_step_local_grads(dibs_engine* e, int32_t t, void* grads_send_dev) {
   if (!e || !grads_send_dev) return fail("null argument");
+  if (e->B > 1) return fail("batched engine: only dibs_engine_run steps it");
   if (!e->has_data) return fail("dibs_engine_set_data has not been called");
   HIP_OK(hipSetDevice(e->cfg.device_id));
   latch_flags(e);
@@ -1371,6 +1716,7 @@ extern "C" int dibs_engine_step_local_grads(dibs_engine* e, int32_t t, void* gra
 // (one event it needs anyway: phase B reads plane 0 as well).
 extern "C" int dibs_engine_kmat_values(dibs_engine* e, const void* vals_all_dev, void* stream) {
   if (!e || !vals_all_dev || !stream) return fail("null argument");
+  if (e->B > 1) return fail("batched engine: only dibs_engine_run steps it");
   HIP_OK(hipSetDevice(e->cfg.device_id));
   const dibs_config& c = e->cfg;
   hipStream_t st = (hipStream_t)stream;
@@ -1399,12 +1745,14 @@ extern "C" int dibs_engine_kmat_values(dibs_engine* e, const void* vals_all_dev,
 
 extern "C" int dibs_engine_step_update_planes(dibs_engine* e, int32_t t, const void* planes_dev, void* vals_send_dev) {
   if (!e || !planes_dev) return fail("null argument");
+  if (e->B > 1) return fail("batched engine: only dibs_engine_run steps it");
   HIP_OK(hipSetDevice(e->cfg.device_id));
   return step_update(e, t, plane_source(e, (const float*)planes_dev), (float*)vals_send_dev);
 }
 
 extern "C" int dibs_engine_step_update(dibs_engine* e, int32_t t, const void* recv_dev) {
   if (!e || !recv_dev) return fail("null argument");
+  if (e->B > 1) return fail("batched engine: only dibs_engine_run steps it");
   HIP_OK(hipSetDevice(e->cfg.device_id));
   return step_update(e, t, packed_source(e, (const float*)recv_dev));
 }
@@ -1414,6 +1762,7 @@ extern "C" int dibs_engine_step_update(dibs_engine* e, int32_t t, const void* re
 extern "C" int dibs_engine_eval_gradients(dibs_engine* e, int32_t t, const uint32_t* keys_theta, const uint32_t* keys_lik, const uint32_t* keys_prior,
                                           float* grad_z_lik, float* baseline_out, float* grad_theta, float* grad_z_prior) {
   if (!e) return fail("null engine");
+  if (e->B > 1) return fail("batched engine: dibs_engine_eval_gradients is not supported");
   if (!e->has_data) return fail("dibs_engine_set_data has not been called");
   const dibs_config& c = e->cfg;
   const bool want_lik = keys_lik != nullptr || keys_theta != nullptr, want_prior = keys_prior != nullptr;
@@ -1532,6 +1881,7 @@ extern "C" int dibs_engine_comm_destroy(dibs_engine* e) {
 
 extern "C" int dibs_engine_comm_init(dibs_engine* e, const void* ids, int32_t n_ids) {
   if (!e) return fail("null argument");
+  if (e->B > 1) return fail("batched engine: a batch is not sharded over ranks");
   if (n_ids < 1 || n_ids > 2) return fail("n_ids must be 1 (one all-gather per step) or 2 (overlapped exchange as well)");
   // ids == NULL: LOOPBACK -- no communicator, the all-gathers are skipped and the rows of the other ranks keep whatever the buffers hold.
   // A measuring device (scripts/gpu_shard_scaling.py: what ONE rank of an N-way run costs per step in this loop, on one GPU), not a
@@ -1566,6 +1916,7 @@ static_assert(DIBS_IPC_HANDLE_BYTES == sizeof(IpcBlob), "include/dibs_hip.h: DIB
 // allocates this rank's exchange arena (zeroed: no exchange has arrived) and writes the blob its peers need to map it
 extern "C" int dibs_engine_ipc_export(dibs_engine* e, void* blob_out) {
   if (!e || !blob_out) return fail("null argument");
+  if (e->B > 1) return fail("batched engine: a batch is not sharded over ranks");
   if (e->cfg.n_ranks > IPC_MAX_RANKS) return fail("the mapped-memory exchange supports at most " + std::to_string(IPC_MAX_RANKS) + " ranks");
   HIP_OK(hipSetDevice(e->cfg.device_id));
   dibs_engine_comm_destroy(e);
@@ -1770,6 +2121,7 @@ static int agree_on_error(dibs_engine* e, unsigned int mine, unsigned int* any) 
 // A flag time-out on ANY rank (see latch_flags) makes ALL ranks repeat the chunk on events from their chunk-start copies of the carry.
 extern "C" int dibs_engine_run_sharded(dibs_engine* e, int32_t t_start, int32_t n_steps, int32_t overlapped) {
   if (!e) return fail("null engine");
+  if (e->B > 1) return fail("batched engine: a batch is not sharded over ranks");
   if (!e->has_data) return fail("dibs_engine_set_data has not been called");
   if (e->n_comms < 1) return fail("dibs_engine_comm_init has not been called");
   if (overlapped && e->n_comms < 2) return fail("the overlapped exchange needs two communicators (dibs_engine_comm_init with n_ids = 2)");
@@ -1864,7 +2216,7 @@ static BufInfo buf_info(const dibs_engine* e, int which) {
     case DIBS_BUF_BASELINE: return {e->baseline, Ml * 4};
     case DIBS_BUF_NODE_SCORES: return {e->node_scores, e->node_scores ? Ml * e->S * e->d * 8 : 0};
     case DIBS_BUF_PARENT_MASKS: return {e->masks, e->masks ? Ml * e->S * e->d * e->W * 8 : 0};
-    case DIBS_BUF_GATHER: return {e->pack, (int64_t)e->M * e->E * 4};
+    case DIBS_BUF_GATHER: return {e->pack, (int64_t)(e->B > 1 ? e->Mloc : e->M) * e->E * 4};
     case DIBS_BUF_GRAD_Z: return {nullptr, Ml * e->D * 4};
     case DIBS_BUF_GRAD_THETA: return {nullptr, Ml * e->P * 4};
     default: return {nullptr, -1};
@@ -1949,6 +2301,7 @@ struct JointWorkGuard {
 extern "C" int dibs_score_graphs(dibs_engine* e, const int32_t* g, const float* theta, int32_t n, const float* x_ho,
                                  const int32_t* mask_ho, int32_t n_ho, float* out) {
   if (!e || !g || !x_ho || !out) return fail("null argument");
+  if (e->B > 1) return fail("batched engine: dibs_score_graphs is not supported (score with a standalone engine)");
   if (n <= 0) return 0;
   HIP_OK(hipSetDevice(e->cfg.device_id));
   HIP_OK(hipStreamSynchronize(e->stream));

@@ -39,6 +39,9 @@ struct BgeParams {
   const double* ldR;    // [n_mats]  logdet R
   double alpha_lambd;
   int n_mats;
+  // batched engines (BATCH instantiations only): every problem's statistics padded to d matrices and stacked problem-major, so that
+  // table row p * d + j ("virtual node") serves node j of problem p = particle / pM; n_mats = n_problems * d
+  int pM;
 };
 
 // A queue entry carries everything the factorisation needs -- {code = (m * d + j) * S + s, j, parent-set words} -- so that the consumer
@@ -106,7 +109,7 @@ __host__ __device__ inline size_t bge_sample_wave_bytes(int d, int S, int W) {
   return ((size_t)S * W * 8 + (size_t)2 * d * 4 + (size_t)S * 4 + 15) & ~(size_t)15;
 }
 
-template <int WAVES, bool SAMPLE>
+template <int WAVES, bool SAMPLE, bool BATCH = false>
 __global__ __launch_bounds__(64 * WAVES) void k_bge_sample(const uint32_t* __restrict__ thr, uint64_t* __restrict__ masks,
                                                            double* __restrict__ node_scores, BgeParams bp, Key2 carry, int m0,
                                                            int M_global, int d, int S, int W, int layout, BgeQueues qs, KmatFuse kf) {
@@ -252,8 +255,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_bge_sample(const uint32_t* __res
     // ---- 2. no parents: closed form (logdet of the empty minor is 0, Schur complement R_jj); the rest is queued by size.
     // Slots are reserved per BLOCK (LDS counters here, one global atomicAdd per tier and block below): same-address global
     // atomics from every wave were the bottleneck while most problems are still queued.
-    const float rjj = bp.Rp[(bp.n_mats > 1 ? (size_t)j * (d + 1) * (d + 1) : 0) + (size_t)j * (d + 1) + j];
-    const double score_l0 = bge_score(bp, j, 0, d, false, 0.f, rjj);
+    // (BATCH: statistics row of node j of this particle's problem)
+    const int jt = BATCH ? ((m0 + m) / bp.pM) * d + j : j;
+    const float rjj = bp.Rp[(bp.n_mats > 1 ? (size_t)jt * (d + 1) * (d + 1) : 0) + (size_t)j * (d + 1) + j];
+    const double score_l0 = bge_score(bp, jt, 0, d, false, 0.f, rjj);
     double* ns_out = node_scores + ((size_t)m * d + j) * S;
     for (int s0 = 0; s0 < S; s0 += 64) {
       const int s = s0 + lane;
@@ -291,7 +296,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_bge_sample(const uint32_t* __res
         const uint32_t tq = v >> 28;
         uint4* dst = qs.list + ((size_t)tq * qs.cap + blk_base[tq] + (v & 0x0FFFFFFFu)) * bge_entry_u4(W);
         const uint64_t w0 = mk[s * W];
-        dst[0] = make_uint4((uint32_t)(((size_t)m * d + j) * S + s), (uint32_t)j, (uint32_t)w0, (uint32_t)(w0 >> 32));
+        dst[0] = make_uint4((uint32_t)(((size_t)m * d + j) * S + s), (uint32_t)(BATCH ? ((m0 + m) / bp.pM) * d + j : j), (uint32_t)w0, (uint32_t)(w0 >> 32));
         if (W > 1) {
           const uint64_t w1 = mk[s * W + 1], w2 = W > 2 ? mk[s * W + 2] : 0ull;
           dst[1] = make_uint4((uint32_t)w1, (uint32_t)(w1 >> 32), (uint32_t)w2, (uint32_t)(w2 >> 32));
@@ -681,9 +686,10 @@ __host__ __device__ inline size_t bge_chol_lds_bytes(int d, bool r_in_lds) {
 // The walk over the work units is software-pipelined: the queue entries of a block's NEXT unit are requested before the current unit is
 // factorised, and a problem's table entries (log-gamma term, N_j, logdet R) as soon as its parent count is known -- at two waves per SIMD
 // (215 registers) nothing else hides those round trips (39 % of the wave cycles were s_waitcnt before: profiles/round2_pmc_lds_window.txt).
-template <bool R_LDS, bool W2>
+template <bool R_LDS, bool W2, bool BATCH = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R_LDS ? 2 : 1))) void k_bge_chol(double* __restrict__ node_scores, BgeParams bp, BgeQueues qs, int d, int S,
                                                   unsigned long long* __restrict__ counters) {
+  static_assert(!(BATCH && R_LDS), "batched statistics are read through the caches");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   __shared__ unsigned int cnt_s[BGE_NQ];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -799,19 +805,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R_LDS ? 2 :
                   uint64_t& w1, Tab& tb) {
     has = ea.y != 0xFFFFFFFFu;
     code = ea.x;
-    jj = has ? (int)ea.y : d;  // (no problem: every index is the padding index)
+    // BATCH: the entry carries the statistics row p * d + j (k_bge_sample); R_LDS is never set there, so PRE holds
+    const int jt = has ? (int)ea.y : d;
+    jj = BATCH && has ? jt % d : jt;  // (no problem: every index is the padding index)
     w0 = ((uint64_t)ea.w << 32) | ea.z;
     w1 = W2 ? (((uint64_t)eb.y << 32) | eb.x) : 0ull;
     l = __popcll(w0) + __popcll(w1);
     if (PRE) {
-      tb.Nn = has ? bp.Nj[jj] : 0.0;
-      tb.g = has ? bp.gam[(size_t)jj * (d + 1) + l] : 0.0;
-      tb.ldRv = has ? bp.ldR[bp.n_mats > 1 ? jj : 0] : 0.0;
+      tb.Nn = has ? bp.Nj[jt] : 0.0;
+      tb.g = has ? bp.gam[(size_t)jt * (d + 1) + l] : 0.0;
+      tb.ldRv = has ? bp.ldR[bp.n_mats > 1 ? jt : 0] : 0.0;
     }
     comp = has && (l + 1 > d - l);
     bge_index_mask(w0, w1, jj, d, comp);
     li = has ? (comp ? d - 1 - l : l) : 0;  // rows before j
-    mat = (int)((comp ? qoff : 0) + ((has && bp.n_mats > 1) ? (long)jj * msz : 0));
+    mat = (int)((comp ? qoff : 0) + ((has && bp.n_mats > 1) ? (long)jt * msz : 0));
   };
   auto store = [&](bool writer, uint32_t code, int jj, const Tab& tb, int l, int li, bool comp, float ld2, float last) {
     if (writer) {
@@ -938,6 +946,7 @@ __host__ __device__ inline size_t bge_wide_wave_bytes(int d) {
   return (((n * (n | 1) + 3) & ~(size_t)3) * 4 + (n + 4) * 4 + 15) & ~(size_t)15;
 }
 #ifdef DIBS_TU_BGE
+template <bool BATCH = false>
 __global__ __launch_bounds__(64 * BGE_WIDE_WAVES) void k_bge_chol_wide(double* __restrict__ node_scores, BgeParams bp, BgeQueues qs, int d, int W) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -952,7 +961,7 @@ __global__ __launch_bounds__(64 * BGE_WIDE_WAVES) void k_bge_chol_wide(double* _
     const uint4 e1 = W > 1 ? lst[(size_t)pi * EW + 1] : make_uint4(0u, 0u, 0u, 0u);
     const uint4 e2 = W > 3 ? lst[(size_t)pi * EW + 2] : make_uint4(0u, 0u, 0u, 0u);
     const uint32_t code = e0.x;
-    const int j = (int)e0.y;
+    const int jt = (int)e0.y, j = BATCH ? jt % d : jt;  // (BATCH: statistics row p * d + j, see k_bge_sample)
     uint64_t w[4] = {((uint64_t)e0.w << 32) | e0.z, ((uint64_t)e1.y << 32) | e1.x, ((uint64_t)e1.w << 32) | e1.z, ((uint64_t)e2.y << 32) | e2.x};
     int l = 0;
 #pragma unroll
@@ -969,7 +978,7 @@ __global__ __launch_bounds__(64 * BGE_WIDE_WAVES) void k_bge_chol_wide(double* _
     }
     const int li = comp ? d - 1 - l : l, n = li + 1;  // rows before j; j goes last
     const float* R = comp ? bp.Qp : bp.Rp;
-    const size_t mat = bp.n_mats > 1 ? (size_t)j * msz : 0;
+    const size_t mat = bp.n_mats > 1 ? (size_t)jt * msz : 0;
     {
       int base = 0;
 #pragma unroll
@@ -991,7 +1000,7 @@ __global__ __launch_bounds__(64 * BGE_WIDE_WAVES) void k_bge_chol_wide(double* _
       float ld2r, lastr;
       bge_chol_wave_reg(R, mat, ldr, d, Lb, idx64, n, li, ld2r, lastr);
       wave_lds_fence();
-      if (lane == 0) node_scores[code] = bge_score(bp, j, l, d, comp, ld2r, lastr);
+      if (lane == 0) node_scores[code] = bge_score(bp, jt, l, d, comp, ld2r, lastr);
       continue;
     }
     float mypiv[2] = {1.f, 1.f};
@@ -1030,7 +1039,7 @@ __global__ __launch_bounds__(64 * BGE_WIDE_WAVES) void k_bge_chol_wide(double* _
     const float ld2 = wave_sum(lg);
     const float last = __shfl(li < 64 ? mypiv[0] : mypiv[1], li & 63, 64);
     wave_lds_fence();
-    if (lane == 0) node_scores[code] = bge_score(bp, j, l, d, comp, ld2, last);
+    if (lane == 0) node_scores[code] = bge_score(bp, jt, l, d, comp, ld2, last);
   }
 }
 

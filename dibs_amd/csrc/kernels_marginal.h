@@ -234,6 +234,42 @@ __global__ __launch_bounds__(256) void k_kmat(const float* __restrict__ pack, si
   kmat_block(smem, pack, pack_stride, seg_off, len, kout, m0, M, scale, h, symmetric, blockIdx.x, blockIdx.y, kadd, ksum);
 }
 
+// ---- batched engines (include/dibs_hip.h: n_problems = B > 1; rows [B * M], problem-major) ----
+// block-diagonal kernel matrix kout [B * M][M]: row a of problem p = a / M against the M particles of p only, by the code of the standalone
+// engine (kmat_block, symmetric: the block's upper triangle mirrored) -- bit-identical entries.  grid = (B * M, ceil(M / KMAT_BT))
+__global__ __launch_bounds__(256) void k_kmat_batch(const float* __restrict__ z, size_t stride, int len, float* __restrict__ kout, int M,
+                                                    float scale, float h) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int a = blockIdx.x, p = a / M;
+  kmat_block(smem, z + (size_t)p * M * stride, stride, 0, len, kout + (size_t)p * M * M, 0, M, scale, h, 1, a - p * M, blockIdx.y);
+}
+// ... the tiled form (standalone engines from DibsTuning::kmat_tiled_min particles): blockIdx.y = problem, one piece per tile (nsplit = 1:
+// the entries do not depend on the cut, see KmatTile).  kt describes ONE problem (x, kout of problem 0)
+__global__ __launch_bounds__(KT_NT) void k_kmat_tile_batch(KmatTile kt) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const size_t p = blockIdx.y;
+  KmatTile k = kt;
+  k.x = kt.x + p * (size_t)kt.M * kt.stride;
+  k.kout = kt.kout + p * (size_t)kt.M * kt.M;
+  kmat_tile_block(smem, k, (int)blockIdx.x, (int)gridDim.x, (int)threadIdx.x);
+}
+// per-problem keys of one step from the B device-resident loop-carry keys (svgd.py:245, 251 per problem): carry_lik = carry, particle m's
+// likelihood key = row 1 + m of split(carry_lik, M + 1), carry_prior = row 0 of it, the prior keys likewise, and the carry advances to row
+// 0 of split(carry_prior, M + 1) -- what step_local / next_carry do on the host for one problem.  grid = B, block = 256
+__global__ __launch_bounds__(256) void k_batch_keys(Key2* __restrict__ carry, Key2* __restrict__ keys_lik, Key2* __restrict__ keys_prior, int M,
+                                                    int layout) {
+  const int p = blockIdx.x;
+  const Key2 c_lik = carry[p];
+  const uint32_t n = (uint32_t)M + 1u;
+  const Key2 c_prior = rng_split_row(c_lik, n, 0u, layout);
+  for (int m = threadIdx.x; m < M; m += blockDim.x) {
+    keys_lik[(size_t)p * M + m] = rng_split_row(c_lik, n, (uint32_t)m + 1u, layout);
+    keys_prior[(size_t)p * M + m] = rng_split_row(c_prior, n, (uint32_t)m + 1u, layout);
+  }
+  __syncthreads();  // (every thread has read carry[p])
+  if (threadIdx.x == 0) carry[p] = rng_split_row(c_prior, n, 0u, layout);
+}
+
 // rmsprop of jax.example_libraries.optimizers (svgd.py:117-120, 265): v <- 0.9 v + (1 - 0.9) phi^2, x <- x - step phi / sqrt(v + 1e-8).
 // Every operation rounded on its own (no contraction into FMAs): the instantiations of k_phi_update / k_phi_gemm are chosen from the SHARD
 // size, and the compiler contracted `v * 0.9f + phi * phi * 0.1f` differently in them -- a 128-particle run on 4 ranks (TA = 4) differed
@@ -279,7 +315,9 @@ __host__ __device__ inline size_t phi_update_lds_bytes(int TA, int M) {
 // FULL: M is a multiple of 64, i.e. every wave's quarter is a whole number of 8-pair batches, whole particle groups, buffer < 4 GiB -- no
 // clamps, no per-pair tests, buffer loads (the headline size, configs 3 and 4); otherwise rows past a quarter repeat its last row and meet zero
 // kernel entries.  JOINT: a second kernel matrix (theta), weights ks = kz + kt and the repulsion of the segment's own kernel.
-template <int TA, bool FULL, bool JOINT>
+// BATCH (batched engines, include/dibs_hip.h n_problems): blockIdx.y = problem p; its M rows of pack / x / v / phi_out and its block
+// [M][M] of the block-diagonal kernel matrix are the whole input of a standalone launch (m0 = 0, Mloc = M): the same sums in the same order.
+template <int TA, bool FULL, bool JOINT, bool BATCH = false>
 __global__ __launch_bounds__(256) void k_phi_update(const float* __restrict__ pack, size_t pack_stride, size_t val_off,
                                                     size_t grad_off, int len, const float* __restrict__ kz,
                                                     const float* __restrict__ kt, int seg_is_theta, float* __restrict__ x,
@@ -292,6 +330,15 @@ __global__ __launch_bounds__(256) void k_phi_update(const float* __restrict__ pa
   // packed rows 16 times per launch: 82 MB of L2 misses).
   const int L = blockIdx.x, c_lo = L & 7, tq = L >> 3, grp = tq % ngroups, bx = (tq / ngroups) * 8 + c_lo;
   if (bx >= ncols) return;  // (block-uniform)
+  if constexpr (BATCH) {
+    static_assert(!JOINT, "batched engines run the marginal model only");
+    const size_t p = blockIdx.y;
+    pack += p * (size_t)M * pack_stride;
+    kz += p * (size_t)M * M;
+    x += p * (size_t)M * len;
+    v += p * (size_t)M * len;
+    if (phi_out) phi_out += p * (size_t)M * len;
+  }
   typedef float f32x2 __attribute__((ext_vector_type(2)));
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* part = smem;  // [4][TA][64] partial sums of the four waves

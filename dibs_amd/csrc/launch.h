@@ -17,6 +17,10 @@ void bge_launch_sample(bool sample, hipStream_t stream, const uint32_t* thr, uin
 size_t bge_sample_lds_bytes(int d, int S, int W);
 void bge_launch_chol(hipStream_t stream, double* node_scores, const BgeParams& bp, const BgeQueues& qs, int d, int S,
                      unsigned long long* counters);
+// batched engines (one launch for every problem; BgeParams::pM set, keys explicit): include/dibs_hip.h, n_problems
+void bge_launch_sample_batch(hipStream_t stream, const uint32_t* thr, uint64_t* masks, double* node_scores, const BgeParams& bp, Key2 carry,
+                             int Mloc, int d, int S, int W, int layout, const BgeQueues& qs);
+void bge_launch_chol_batch(hipStream_t stream, double* node_scores, const BgeParams& bp, const BgeQueues& qs, int d, int S);
 void bge_launch_sum_nodes(hipStream_t stream, const double* node_scores, float* out, int d, int S);
 
 // ---- tu_acyc.hip -------------------------------------------------------------------------------------

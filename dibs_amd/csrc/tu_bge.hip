@@ -32,8 +32,8 @@ void bge_launch_chol(hipStream_t stream, double* node_scores, const BgeParams& b
                      unsigned long long* counters) {
   if (d > 128) {  // three or four mask words: one problem per wave, everything in the last tier (k_bge_chol_wide)
     const size_t lw = BGE_WIDE_WAVES * bge_wide_wave_bytes(d);
-    allow_lds(k_bge_chol_wide, lw);
-    hipLaunchKernelGGL(k_bge_chol_wide, dim3(2048), dim3(64 * BGE_WIDE_WAVES), lw, stream, node_scores, bp, qs, d, (d + 63) / 64);
+    allow_lds(k_bge_chol_wide<false>, lw);
+    hipLaunchKernelGGL(k_bge_chol_wide<false>, dim3(2048), dim3(64 * BGE_WIDE_WAVES), lw, stream, node_scores, bp, qs, d, (d + 63) / 64);
     return;
   }
   const bool w2 = d > 64;
@@ -51,6 +51,36 @@ void bge_launch_chol(hipStream_t stream, double* node_scores, const BgeParams& b
   else if (!w2) CHOL(false, false)
   else CHOL(false, true)
 #undef CHOL
+}
+
+// batched engines (BgeParams::pM particles per problem, statistics stacked problem-major): the BATCH instantiations, no kernel-matrix
+// blocks, matrices read through the caches
+void bge_launch_sample_batch(hipStream_t stream, const uint32_t* thr, uint64_t* masks, double* node_scores, const BgeParams& bp, Key2 carry,
+                             int Mloc, int d, int S, int W, int layout, const BgeQueues& qs) {
+  const size_t lds = bge_sample_lds_bytes(d, S, W);
+  const KmatFuse kf{nullptr, nullptr, 0, 0, 0, 0.f, 0.f, nullptr, 0u};
+  allow_lds(k_bge_sample<4, true, true>, lds);
+  // (M = -1: explicit per-particle keys, see rng_explicit_row)
+  hipLaunchKernelGGL((k_bge_sample<4, true, true>), dim3((d + 3) / 4, Mloc), dim3(256), lds, stream, thr, masks, node_scores, bp, carry, 0, -1, d,
+                     S, W, layout, qs, kf);
+}
+
+void bge_launch_chol_batch(hipStream_t stream, double* node_scores, const BgeParams& bp, const BgeQueues& qs, int d, int S) {
+  if (d > 128) {
+    const size_t lw = BGE_WIDE_WAVES * bge_wide_wave_bytes(d);
+    allow_lds(k_bge_chol_wide<true>, lw);
+    hipLaunchKernelGGL(k_bge_chol_wide<true>, dim3(2048), dim3(64 * BGE_WIDE_WAVES), lw, stream, node_scores, bp, qs, d, (d + 63) / 64);
+    return;
+  }
+  const size_t lds = bge_chol_lds_bytes(d, false);
+  unsigned long long* const none = nullptr;
+  if (d > 64) {
+    allow_lds(k_bge_chol<false, true, true>, lds);
+    hipLaunchKernelGGL((k_bge_chol<false, true, true>), dim3(512), dim3(256), lds, stream, node_scores, bp, qs, d, S, none);
+  } else {
+    allow_lds(k_bge_chol<false, false, true>, lds);
+    hipLaunchKernelGGL((k_bge_chol<false, false, true>), dim3(512), dim3(256), lds, stream, node_scores, bp, qs, d, S, none);
+  }
 }
 
 void bge_launch_sum_nodes(hipStream_t stream, const double* node_scores, float* out, int d, int S) {

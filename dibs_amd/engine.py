@@ -23,7 +23,8 @@ class Engine:
             raise ValueError("pass the handle of a non-default stream (e.g. torch.cuda.Stream().cuda_stream) or None")
         _lib.check(self.lib.dibs_engine_create(C.byref(cfg), C.c_void_p(stream) if stream else None, C.byref(self._h)))
         self.M, self.d, self.k = cfg.n_particles, cfg.n_vars, cfg.n_dim
-        self.Mloc = cfg.n_particles // cfg.n_ranks
+        self.B = max(int(cfg.reserved_i[0]), 1)   # problems of a batched engine (include/dibs_hip.h): rows [B * M], problem-major
+        self.Mloc = self.B * cfg.n_particles if self.B > 1 else cfg.n_particles // cfg.n_ranks
         self.P = int(self.lib.dibs_engine_theta_size(self._h))
         self.state_gen = 0   # bumped whenever the particles are replaced from outside (init_particles / set_state): the overlapped
                              # exchange of dibs_amd.distributed compares it with the generation its gathered values belong to
@@ -46,6 +47,29 @@ class Engine:
         mo = None if bge_mean_obs is None else np.ascontiguousarray(bge_mean_obs, np.float32)
         _lib.check(self.lib.dibs_engine_set_data(self._h, _ptr(x), _ptr(m), _ptr(mo)))
 
+    # batched engine (n_problems > 1): per-problem data, particles and loop-carry keys
+    def set_data_problem(self, p, x, interv_mask=None, bge_mean_obs=None):
+        x = np.ascontiguousarray(x, np.float32)
+        assert x.ndim == 2 and x.shape[1] == self.d, x.shape
+        m = None if interv_mask is None else np.ascontiguousarray(interv_mask, np.int32)
+        assert m is None or m.shape == x.shape, m.shape
+        mo = None if bge_mean_obs is None else np.ascontiguousarray(bge_mean_obs, np.float32)
+        _lib.check(self.lib.dibs_engine_set_data_problem(self._h, int(p), _ptr(x), int(x.shape[0]), _ptr(m), _ptr(mo)))
+
+    def init_particles_batch(self, keys):
+        keys = np.ascontiguousarray(np.asarray(keys, np.uint32).reshape(self.B, 2))
+        _lib.check(self.lib.dibs_engine_init_particles_batch(self._h, _ptr(keys)))
+        self.state_gen += 1
+
+    def get_keys(self):
+        keys = np.empty((self.B, 2), np.uint32)
+        _lib.check(self.lib.dibs_engine_get_keys(self._h, _ptr(keys)))
+        return keys
+
+    def set_keys(self, keys):
+        keys = np.ascontiguousarray(np.asarray(keys, np.uint32).reshape(self.B, 2))
+        _lib.check(self.lib.dibs_engine_set_keys(self._h, _ptr(keys)))
+
     def init_particles(self, key):
         key = np.ascontiguousarray(key, np.uint32).reshape(2)
         _lib.check(self.lib.dibs_engine_init_particles(self._h, _ptr(key)))
@@ -64,10 +88,12 @@ class Engine:
         v_z = np.empty_like(z)
         theta = np.empty((self.Mloc, self.P), np.float32) if self.P else None
         v_theta = np.empty_like(theta) if self.P else None
-        key = np.empty(2, np.uint32)
+        key = np.empty(2, np.uint32) if self.B == 1 else None   # (batched engine: the B carries come from get_keys)
         baseline = np.empty(self.Mloc, np.float32)
         _lib.check(self.lib.dibs_engine_get_state(self._h, _ptr(z), _ptr(v_z), _ptr(theta), _ptr(v_theta), _ptr(key),
                                                   _ptr(baseline)))
+        if key is None:
+            key = self.get_keys()
         return dict(z=z, v_z=v_z, theta=theta, v_theta=v_theta, key=key, baseline=baseline)
 
     def run(self, t_start, n_steps):

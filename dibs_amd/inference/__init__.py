@@ -1,2 +1,3 @@
 from .dibs import DiBS  # noqa: F401
 from .svgd import MarginalDiBS, JointDiBS  # noqa: F401
+from .batch import sample_batch  # noqa: F401

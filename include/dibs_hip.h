@@ -57,7 +57,7 @@ typedef struct dibs_config {
   int32_t rank;             /* particle shard: this engine owns particles                            */
   int32_t n_ranks;          /*   [rank*M/n_ranks, (rank+1)*M/n_ranks)                                */
   int32_t device_id;
-  int32_t reserved_i[5];
+  int32_t reserved_i[5];    /* [0] n_problems: 0 / 1 = one problem; B > 1 = a batched engine (see dibs_engine_set_data_problem) */
 
   double alpha_linear;      /* dibs.py:70 */
   double beta_linear;       /* dibs.py:71 */
@@ -213,6 +213,23 @@ int dibs_engine_gather_particles(dibs_engine* e, float* z_all, float* theta_all)
 #define DIBS_IPC_HANDLE_BYTES 128
 int dibs_engine_ipc_export(dibs_engine* e, void* blob_out);
 int dibs_engine_comm_init_ipc(dibs_engine* e, const void* blobs_all);
+
+/* BATCHED ENGINE (no reference counterpart; the JAX equivalent is vmap of the SVGD loop over keys and data): dibs_config.reserved_i[0] =
+ * n_problems = B > 1 makes one engine hold B independent MarginalDiBS + BGe problems (score-function estimator, one rank).  They share
+ * every size (d, k, n_particles = M PER PROBLEM, S, Sa), the graph prior and every hyper-parameter; each has its own data, intervention mask,
+ * PRNG key and M particles.  Device arrays hold B * M rows, problem-major: dibs_engine_get_state / set_state / read_buffer see all of them
+ * (their key argument must be NULL), and each launch of a step covers the whole batch.  Problem p ends bit-identical to a standalone engine
+ * run with (x_p, mask_p, key_p) and the same chunking.  dibs_engine_create rejects joint models, the reparam estimator, n_ranks != 1 and
+ * n_particles >= 256; dibs_engine_set_data / init_particles / eval_gradients / step_* / the sharded loop and dibs_score_graphs are refused.
+ *   dibs_engine_set_data_problem(e, p, x, n_obs, mask, mean_obs)  the BGe statistics of problem p (x: f32 [n_obs, d]; n_obs may differ
+ *                                                                 between problems; mask: i32 [n_obs, d] or NULL; mean_obs: f32 [d] or NULL)
+ *   dibs_engine_init_particles_batch(e, keys)                      keys: u32 [B][2]; problem p as dibs_engine_init_particles(keys[p])
+ *   dibs_engine_get_keys / dibs_engine_set_keys(e, keys)           the B loop-carry keys, u32 [B][2] */
+int dibs_engine_set_data_problem(dibs_engine* e, int32_t p, const float* x, int32_t n_obs, const int32_t* interv_mask,
+                                 const float* bge_mean_obs);
+int dibs_engine_init_particles_batch(dibs_engine* e, const uint32_t* keys);
+int dibs_engine_get_keys(dibs_engine* e, uint32_t* keys);
+int dibs_engine_set_keys(dibs_engine* e, const uint32_t* keys);
 
 /* debugging / parity: copy a device buffer to the host (nbytes must match); theta size query */
 int dibs_engine_read_buffer(dibs_engine* e, int32_t which, void* host, int64_t nbytes);
