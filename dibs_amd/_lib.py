@@ -23,6 +23,7 @@ EXPORTS = [
     "dibs_engine_comm_destroy", "dibs_engine_run_sharded", "dibs_engine_gather_particles", "dibs_engine_ipc_export",
     "dibs_engine_comm_init_ipc", "dibs_engine_flag_fallbacks", "dibs_engine_debug_drop_next_flag",
     "dibs_engine_set_data_problem", "dibs_engine_init_particles_batch", "dibs_engine_get_keys", "dibs_engine_set_keys",
+    "dibs_engine_set_data_f64", "dibs_engine_set_state_f64", "dibs_engine_get_state_f64", "dibs_engine_precision",
 ]
 
 
@@ -101,6 +102,10 @@ def load():
     lib.dibs_engine_init_particles_batch.argtypes = [vp, vp]
     lib.dibs_engine_get_keys.argtypes = [vp, vp]
     lib.dibs_engine_set_keys.argtypes = [vp, vp]
+    lib.dibs_engine_set_data_f64.argtypes = [vp, vp, vp, vp]
+    lib.dibs_engine_set_state_f64.argtypes = [vp] + [vp] * 6
+    lib.dibs_engine_get_state_f64.argtypes = [vp] + [vp] * 6
+    lib.dibs_engine_precision.argtypes = [vp]
     for name in EXPORTS:
         if name not in ("dibs_last_error", "dibs_abi_version", "dibs_engine_gather_elems_per_rank", "dibs_engine_plane_elems_per_rank",
                         "dibs_engine_buffer_bytes", "dibs_engine_theta_size"):

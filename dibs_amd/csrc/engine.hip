@@ -62,8 +62,25 @@ struct BgeStats {
   BgeParams params() const { return BgeParams{Rp, Qp, gam, Nj, ldR, alpha_lambd, n_mats}; }
 };
 
+// the float64 engine's device state (dibs_config.reserved_i[1] = 64; kernels_f64.h): loop carry, per-step buffers and the BGe statistics in
+// double.  The parent sets and node scores go to the f32 engine's PARENT_MASKS / NODE_SCORES buffers (same layouts).
+struct F64State {
+  double *z = nullptr, *vz = nullptr, *baseline = nullptr, *scores = nullptr, *probs = nullptr, *w_lik = nullptr, *w_acyc = nullptr,
+         *part = nullptr, *logprobs = nullptr, *gradz = nullptr, *kxx = nullptr, *phi = nullptr, *R = nullptr, *Nj = nullptr, *gam = nullptr;
+  uint32_t* thr = nullptr;
+  float* ltab = nullptr;  // [2^23] the acyclicity noise: logistic value of every f32 uniform (f64_logistic_table)
+  double alpha_lambd = 0;
+  int n_mats = 1;
+  ~F64State() {
+    void* ptrs[] = {z, vz, baseline, scores, probs, w_lik, w_acyc, part, logprobs, gradz, kxx, phi, R, Nj, gam, thr, ltab};
+    for (void* p_ : ptrs)
+      if (p_) hipFree(p_);
+  }
+};
+
 struct dibs_engine {
   dibs_config cfg;
+  F64State* f64 = nullptr;  // float64 engine (see F64State); null: the f32 engine
   DibsTuning tune;  // the environment switches (tuning.h), latched at creation
   int d, k, M, Mloc, m0, N, S, Sa, W;
   // batched engine (cfg.reserved_i[0] = n_problems = B > 1): B independent problems of M particles each; the device arrays hold Mloc = B * M
@@ -329,6 +346,16 @@ static int engine_alloc(dibs_engine* e, const dibs_config& c, void* stream) {
     }
     e->streams_concurrent = it->second;
   }
+  if (c.reserved_i[1] == 64) {
+    // float64 engine: of the f32 engine's buffers only the parent sets and node scores (same layouts) and the counters; F64State (f64_alloc)
+    // holds everything else
+    const size_t Ml = e->Mloc;
+    HIP_OK(dalloc(&e->masks, Ml * e->S * e->d * e->W));
+    HIP_OK(dalloc(&e->node_scores, Ml * e->S * e->d));
+    HIP_OK(dalloc(&e->counters, (size_t)DIBS_N_COUNTERS));
+    hipDeviceSynchronize();
+    return 0;
+  }
   const size_t Ml = e->Mloc, dd = (size_t)e->d * e->d;
   HIP_OK(dalloc(&e->z, Ml * e->D));
   HIP_OK(dalloc(&e->vz, Ml * e->D));
@@ -411,12 +438,92 @@ static int engine_alloc(dibs_engine* e, const dibs_config& c, void* stream) {
   return 0;
 }
 
+// The float64 engine's draws whose value passes through a C-library function rounded to float: jax.random.normal's -log1p (erfinv) and
+// jax.random.logistic's logf.  The f64 oracle (oracle/dibs_oracle.c: normal_from_bits, logistic_from_bits) calls the C library; no device
+// math library rounds exactly as it does (glibc's logf differs from the correctly rounded value for ~0.5 % of these arguments, and its
+// variant depends on the CPU).  So these values come from the host's C library, in the oracle's operation order: the initial normal draws
+// directly (dibs_engine_init_particles, once per run), the logistic draws through a table over all 2^23 f32 uniforms (an f32 uniform is
+// (bits >> 9) * 2^-23 mapped onto [lo, 1): 23 bits decide it), built once per process and flag and read by k64_acyc.
+static float f64_host_normal(uint32_t bits) {
+  static const float A[9] = {2.81022636e-08f, 3.43273939e-07f, -3.5233877e-06f, -4.39150654e-06f, 0.00021858087f,
+                             -0.00125372503f, -0.00417768164f, 0.246640727f, 1.50140941f};
+  static const float B[9] = {-0.000200214257f, 0.000100950558f, 0.00134934322f, -0.00367342844f, 0.00573950773f,
+                             -0.0076224613f, 0.00943887047f, 1.00167406f, 2.83297682f};
+  const float x = rng_uniform(bits, -0.99999994f, 1.0f);  // (host: every operation rounded on its own, rng.h)
+  volatile float xx = -x * x;
+  float w = (float)(-log1p((double)xx));
+  const float* cf = w < 5.0f ? A : B;
+  w = w < 5.0f ? w - 2.5f : sqrtf(w) - 3.0f;
+  float p = cf[0];
+  for (int i = 1; i < 9; ++i) {
+    volatile float pw = p * w;
+    p = cf[i] + pw;
+  }
+  volatile float px = p * x;
+  return 1.41421354f * px;
+}
+static const float* f64_logistic_table(int tiny) {
+  static std::mutex mu;
+  static std::vector<float> tab[2];
+  std::lock_guard<std::mutex> lock(mu);
+  std::vector<float>& t = tab[tiny ? 1 : 0];
+  if (t.empty()) {
+    t.resize((size_t)1 << 23);
+    const float lo = tiny ? 1.17549435e-38f : 1.1920929e-07f;
+    for (uint32_t i = 0; i < (1u << 23); ++i) {
+      const float x = rng_uniform(i << 9, lo, 1.0f);
+      volatile float q = x / (1.0f - x);
+      t[i] = logf(q);
+    }
+  }
+  return t.data();
+}
+
+// the float64 engine's buffers (after engine_alloc, which allocated the parent-set and node-score buffers of the same layouts as the f32
+// engine's)
+static int f64_alloc(dibs_engine* e) {
+  e->f64 = new F64State();
+  F64State& f = *e->f64;
+  const size_t Ml = e->Mloc, dd = (size_t)e->d * e->d;
+  HIP_OK(dalloc(&f.ltab, (size_t)1 << 23));
+  HIP_OK(hipMemcpy(f.ltab, f64_logistic_table(e->cfg.logistic_minval_tiny), ((size_t)1 << 23) * 4, hipMemcpyHostToDevice));
+  HIP_OK(dalloc(&f.z, Ml * e->D));
+  HIP_OK(dalloc(&f.vz, Ml * e->D));
+  HIP_OK(dalloc(&f.baseline, Ml));
+  HIP_OK(dalloc(&f.scores, Ml * dd));
+  HIP_OK(dalloc(&f.probs, Ml * dd));
+  HIP_OK(dalloc(&f.thr, Ml * dd));
+  HIP_OK(dalloc(&f.w_lik, Ml * dd));
+  HIP_OK(dalloc(&f.w_acyc, Ml * dd));
+  HIP_OK(dalloc(&f.part, Ml * e->Sa * dd));
+  HIP_OK(dalloc(&f.logprobs, Ml * e->S));
+  HIP_OK(dalloc(&f.gradz, Ml * e->D));
+  HIP_OK(dalloc(&f.kxx, Ml * e->M));
+  HIP_OK(dalloc(&f.phi, Ml * e->D));
+  hipDeviceSynchronize();  // (the zero fills ran on the null stream)
+  return 0;
+}
 
 extern "C" int dibs_engine_create(const dibs_config* cfg, void* stream, dibs_engine** out) {
   if (!cfg || !out) return fail("null argument");
   *out = nullptr;
   const dibs_config& c = *cfg;
   if (c.abi_version != DIBS_ABI_VERSION) return fail("dibs_config.abi_version mismatch");
+  {
+    // precision (reserved_i[1]): 0 / 32 = float32, 64 = the float64 engine (MarginalDiBS + BGe + score estimator, one rank, one problem)
+    const int prec = c.reserved_i[1];
+    if (prec != 0 && prec != 32 && prec != 64)
+      return fail("float64 engine: dibs_config.reserved_i[1] (precision) must be 0 or 32 (float32) or 64 (float64), got " + std::to_string(prec));
+    if (prec == 64) {
+      if (c.joint) return fail("float64 engine: joint models are not supported (MarginalDiBS + BGe only)");
+      if (c.likelihood != DIBS_LIK_BGE) return fail("float64 engine: only the BGe marginal likelihood is supported");
+      if (c.grad_estimator_z != DIBS_EST_SCORE) return fail("float64 engine: the reparam estimator is not supported (score-function estimator only)");
+      if (c.n_ranks != 1) return fail("float64 engine: n_ranks must be 1");
+      if (c.reserved_i[0] > 1) return fail("float64 engine: n_problems must be 1 (no batched float64 engine)");
+      if (c.n_vars < 2 || c.n_vars > 64) return fail("float64 engine: n_vars must be in [2, 64]");
+      if (c.n_particles > 1024) return fail("float64 engine: n_particles must be <= 1024");
+    }
+  }
   if (c.n_vars < 2 || c.n_vars > 256) return fail("n_vars must be in [2, 256]");
   // 113 .. 256 variables: the LDS-resident kernels give way to the global-memory paths (kernels_acyc_big.h, k_backproject_big, chunked
   // k_edge_scores, k_bge_chol_wide)
@@ -503,7 +610,7 @@ extern "C" int dibs_engine_create(const dibs_config* cfg, void* stream, dibs_eng
 
   dibs_engine* e = new dibs_engine();  // value-initialised: every POD member starts at zero
   g_live_engines.fetch_add(1);
-  if (engine_alloc(e, c, stream)) {
+  if (engine_alloc(e, c, stream) || (c.reserved_i[1] == 64 && f64_alloc(e))) {
     const std::string msg = g_err;
     dibs_engine_destroy(e);  // frees whatever had been allocated (stream, events, buffers)
     g_err = msg;
@@ -525,6 +632,7 @@ extern "C" int dibs_engine_destroy(dibs_engine* e) {
   for (void* p : ptrs)
     if (p) hipFree(p);
   joint_free(&e->jw);
+  delete e->f64;
   dibs_engine_comm_destroy(e);
   if (e->stream2) hipStreamDestroy(e->stream2);
   if (e->ev_fork) hipEventDestroy(e->ev_fork);
@@ -679,6 +787,12 @@ static int bge_prepare(BgeStats* st, const dibs_config& cfg, int d, int N, const
 extern "C" int dibs_engine_set_data(dibs_engine* e, const float* x, const int32_t* interv_mask, const float* bge_mean_obs) {
   if (!e || !x) return fail("null argument");
   if (e->B > 1) return fail("batched engine: use dibs_engine_set_data_problem");
+  if (e->f64) {  // float64 engine: the data widened exactly
+    const size_t n = (size_t)e->N * e->d;
+    std::vector<double> x64(x, x + n), mo64;
+    if (bge_mean_obs) mo64.assign(bge_mean_obs, bge_mean_obs + e->d);
+    return dibs_engine_set_data_f64(e, x64.data(), interv_mask, bge_mean_obs ? mo64.data() : nullptr);
+  }
   HIP_OK(hipSetDevice(e->cfg.device_id));
   HIP_OK(hipStreamSynchronize(e->stream));
   e->score_cache.valid = false;  // (the BGe prior mean travels with the data)
@@ -716,6 +830,19 @@ extern "C" int dibs_engine_init_particles(dibs_engine* e, const uint32_t key[2])
   const Key2 ikey = rng_split_row(subk, 2, 0, L);          // key, subk = split(key)            svgd.py:145 / :509
   const Key2 isub = rng_split_row(subk, 2, 1, L);
   const uint64_t ntot = (uint64_t)e->M * e->D, nloc = (uint64_t)e->Mloc * e->D;
+  if (e->f64) {  // float64 engine: z = (double)(normal_f32 * std_f32), the oracle's orc_init_particles (see f64_host_normal)
+    std::vector<double> z(nloc);
+    for (uint64_t i = 0; i < nloc; ++i) {
+      volatile float v = f64_host_normal(rng_bits_at(isub, ntot, (uint64_t)e->m0 * e->D + i, L)) * e->sigz;
+      z[i] = (double)v;
+    }
+    HIP_OK(hipStreamSynchronize(e->stream));
+    HIP_OK(hipMemcpy(e->f64->z, z.data(), nloc * 8, hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(e->f64->vz, 0, nloc * 8));
+    HIP_OK(hipMemset(e->f64->baseline, 0, (size_t)e->Mloc * 8));
+    HIP_OK(hipDeviceSynchronize());
+    return 0;
+  }
   hipLaunchKernelGGL(k_init_z, dim3((unsigned)((nloc + 255) / 256)), dim3(256), 0, e->stream, e->z, isub, ntot,
                      (uint64_t)e->m0 * e->D, nloc, e->sigz, L);
   if (e->cfg.joint) {
@@ -745,6 +872,7 @@ extern "C" int dibs_engine_init_particles(dibs_engine* e, const uint32_t key[2])
 extern "C" int dibs_engine_set_state(dibs_engine* e, const float* z, const float* v_z, const float* theta,
                                      const float* v_theta, const uint32_t* key, const float* baseline) {
   if (!e) return fail("null engine");
+  if (e->f64) return fail("float64 engine: use dibs_engine_set_state_f64 (the f32 state accessors would round)");
   if (e->B > 1 && key) return fail("batched engine: the loop-carry keys go through dibs_engine_set_keys (key must be null)");
   HIP_OK(hipSetDevice(e->cfg.device_id));
   HIP_OK(hipStreamSynchronize(e->stream));
@@ -764,6 +892,7 @@ extern "C" int dibs_engine_set_state(dibs_engine* e, const float* z, const float
 extern "C" int dibs_engine_get_state(dibs_engine* e, float* z, float* v_z, float* theta, float* v_theta, uint32_t* key,
                                      float* baseline) {
   if (!e) return fail("null engine");
+  if (e->f64) return fail("float64 engine: use dibs_engine_get_state_f64 (the f32 state accessors would round)");
   if (e->B > 1 && key) return fail("batched engine: the loop-carry keys go through dibs_engine_get_keys (key must be null)");
   HIP_OK(hipSetDevice(e->cfg.device_id));
   HIP_OK(hipStreamSynchronize(e->stream));
@@ -1639,6 +1768,98 @@ static int run_steps_batch(dibs_engine* e, int t_start, int n_steps) {
   return 0;
 }
 
+// ---- float64 engine (dibs_config.reserved_i[1] = 64, include/dibs_hip.h; kernels_f64.h) ----------------------------------------------
+// One step: the loop-carry key advances as in step_local (split for the likelihood, then for the prior); edge scores on the main stream,
+// the acyclicity chains, their reduction and the kernel matrix on the second stream (fork / join by events, as step_batch), BGe sampling and
+// node scores -> weights -> per-particle gradient -> phi -> optimizer on the main stream.
+static int step_f64(dibs_engine* e, int t) {
+  const dibs_config& c = e->cfg;
+  const F64State& f = *e->f64;
+  F64Args a{};
+  a.d = e->d; a.k = e->k; a.M = e->M; a.S = e->S; a.Sa = e->Sa; a.dpad = e->dpad; a.L = c.rng_layout; a.tiny = c.logistic_minval_tiny;
+  a.prior = c.graph_prior; a.opt = c.optimizer; a.n_mats = f.n_mats; a.D = e->D;
+  a.alpha = c.alpha_linear * t;
+  a.beta = c.beta_linear * t;
+  a.tau = c.tau;
+  a.er_c = 0.0;
+  if (c.graph_prior == DIBS_PRIOR_ER) {
+    const double p = c.graph_prior_edges_per_node * e->d / ((e->d * (e->d - 1)) / 2.0);
+    a.er_c = log(p) - log(1 - p);
+  }
+  const double sigz = c.latent_prior_std > 0 ? c.latent_prior_std : (double)(1.0f / sqrtf((float)e->k));  // (the oracle's latent_std)
+  a.inv_sig2 = 1.0 / (sigz * sigz);
+  a.sfb = c.score_function_baseline;
+  a.h = c.h_latent;
+  a.scale = c.scale_latent;
+  a.step = c.stepsize;
+  a.alpha_lambd = f.alpha_lambd;
+  a.carry_lik = e->key;
+  a.carry_prior = next_carry(e, a.carry_lik);
+  e->key = next_carry(e, a.carry_prior);
+  a.z = f.z; a.vz = f.vz; a.baseline = f.baseline; a.scores = f.scores; a.probs = f.probs; a.w_lik = f.w_lik; a.w_acyc = f.w_acyc;
+  a.part = f.part; a.logprobs = f.logprobs; a.gradz = f.gradz; a.kxx = f.kxx; a.phi = f.phi; a.thr = f.thr; a.masks = e->masks;
+  a.node_scores = e->node_scores; a.R = f.R; a.Nj = f.Nj; a.gam = f.gam; a.ltab = f.ltab;
+  {
+    KTimer tm(e, DIBS_K_EDGE);
+    f64_launch_edge(e->stream, a);
+  }
+  const bool fork = e->stream2 != nullptr, join_now = e->profiling && !e->profiling_concurrent;
+  hipStream_t s2 = fork ? e->stream2 : e->stream;
+  if (fork) {
+    HIP_OK(hipEventRecord(e->ev_fork, e->stream));
+    HIP_OK(hipStreamWaitEvent(e->stream2, e->ev_fork, 0));
+  }
+  {
+    KTimer tm(e, DIBS_K_ACYC, s2);
+    f64_launch_acyc(s2, a);
+  }
+  {
+    KTimer tm(e, DIBS_K_ACYC_REDUCE, s2);
+    f64_launch_acyc_reduce(s2, a);
+  }
+  {
+    KTimer tm(e, DIBS_K_KMAT, s2);
+    f64_launch_kmat(s2, a);
+  }
+  if (fork) {
+    HIP_OK(hipEventRecord(e->ev_join, e->stream2));
+    if (join_now) HIP_OK(hipStreamWaitEvent(e->stream, e->ev_join, 0));
+  }
+  {
+    KTimer tm(e, DIBS_K_BGE_NODES);
+    f64_launch_bge(e->stream, a);
+  }
+  {
+    KTimer tm(e, DIBS_K_LIK_WEIGHTS);
+    f64_launch_weights(e->stream, a);
+  }
+  if (fork && !join_now) HIP_OK(hipStreamWaitEvent(e->stream, e->ev_join, 0));
+  {
+    KTimer tm(e, DIBS_K_ZGRAD);
+    f64_launch_grad(e->stream, a);
+  }
+  {
+    KTimer tm(e, DIBS_K_PHI_UPDATE);
+    f64_launch_phi(e->stream, a);
+    f64_launch_update(e->stream, a);
+  }
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(err));
+  return 0;
+}
+
+static int run_steps_f64(dibs_engine* e, int t_start, int n_steps) {
+  for (int t = t_start; t < t_start + n_steps; ++t) {
+    if (step_f64(e, t)) return 1;
+    if (e->profiling && e->pending.size() > 4096) drain_timers(e);
+  }
+  HIP_OK(hipStreamSynchronize(e->stream));
+  if (e->stream2) HIP_OK(hipStreamSynchronize(e->stream2));
+  if (e->profiling) drain_timers(e);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 extern "C" int dibs_engine_run(dibs_engine* e, int32_t t_start, int32_t n_steps) {
   if (!e) return fail("null engine");
   if (e->B > 1 && !e->has_data) return fail("dibs_engine_set_data_problem has not been called for every problem");
@@ -1646,6 +1867,10 @@ extern "C" int dibs_engine_run(dibs_engine* e, int32_t t_start, int32_t n_steps)
   if (e->B > 1) {
     HIP_OK(hipSetDevice(e->cfg.device_id));
     return run_steps_batch(e, t_start, n_steps);
+  }
+  if (e->f64) {
+    HIP_OK(hipSetDevice(e->cfg.device_id));
+    return run_steps_f64(e, t_start, n_steps);
   }
   if (e->cfg.n_ranks != 1) return fail("dibs_engine_run is single-rank; use step_local / step_update");
   HIP_OK(hipSetDevice(e->cfg.device_id));
@@ -1677,6 +1902,7 @@ extern "C" int dibs_engine_debug_drop_next_flag(dibs_engine* e) {
 
 extern "C" int dibs_engine_step_local(dibs_engine* e, int32_t t, void* send_dev) {
   if (!e || !send_dev) return fail("null argument");
+  if (e->f64) return fail("float64 engine: dibs_engine_step_local is not supported (dibs_engine_run only)");
   if (e->B > 1) return fail("batched engine: only dibs_engine_run steps it");
   if (!e->has_data) return fail("dibs_engine_set_data has not been called");
   HIP_OK(hipSetDevice(e->cfg.device_id));
@@ -1691,6 +1917,7 @@ extern "C" int64_t dibs_engine_plane_elems_per_rank(const dibs_engine* e) { retu
 
 extern "C" int dibs_engine_export_values(dibs_engine* e, void* vals_send_dev) {
   if (!e || !vals_send_dev) return fail("null argument");
+  if (e->f64) return fail("float64 engine: dibs_engine_export_values is not supported (dibs_engine_run only)");
   HIP_OK(hipSetDevice(e->cfg.device_id));
   float* dst = (float*)vals_send_dev;
   HIP_OK(hipMemcpy2DAsync(dst, (size_t)e->Ev * 4, e->z, (size_t)e->D * 4, (size_t)e->D * 4, (size_t)e->Mloc, hipMemcpyDeviceToDevice, e->stream));
@@ -1702,6 +1929,7 @@ extern "C" int dibs_engine_export_values(dibs_engine* e, void* vals_send_dev) {
 
 extern "C" int dibs_engine_step_local_grads(dibs_engine* e, int32_t t, void* grads_send_dev) {
   if (!e || !grads_send_dev) return fail("null argument");
+  if (e->f64) return fail("float64 engine: dibs_engine_step_local_grads is not supported (dibs_engine_run only)");
   if (e->B > 1) return fail("batched engine: only dibs_engine_run steps it");
   if (!e->has_data) return fail("dibs_engine_set_data has not been called");
   HIP_OK(hipSetDevice(e->cfg.device_id));
@@ -1716,6 +1944,7 @@ extern "C" int dibs_engine_step_local_grads(dibs_engine* e, int32_t t, void* gra
 // (one event it needs anyway: phase B reads plane 0 as well).
 extern "C" int dibs_engine_kmat_values(dibs_engine* e, const void* vals_all_dev, void* stream) {
   if (!e || !vals_all_dev || !stream) return fail("null argument");
+  if (e->f64) return fail("float64 engine: dibs_engine_kmat_values is not supported (dibs_engine_run only)");
   if (e->B > 1) return fail("batched engine: only dibs_engine_run steps it");
   HIP_OK(hipSetDevice(e->cfg.device_id));
   const dibs_config& c = e->cfg;
@@ -1745,6 +1974,7 @@ extern "C" int dibs_engine_kmat_values(dibs_engine* e, const void* vals_all_dev,
 
 extern "C" int dibs_engine_step_update_planes(dibs_engine* e, int32_t t, const void* planes_dev, void* vals_send_dev) {
   if (!e || !planes_dev) return fail("null argument");
+  if (e->f64) return fail("float64 engine: dibs_engine_step_update_planes is not supported (dibs_engine_run only)");
   if (e->B > 1) return fail("batched engine: only dibs_engine_run steps it");
   HIP_OK(hipSetDevice(e->cfg.device_id));
   return step_update(e, t, plane_source(e, (const float*)planes_dev), (float*)vals_send_dev);
@@ -1752,6 +1982,7 @@ extern "C" int dibs_engine_step_update_planes(dibs_engine* e, int32_t t, const v
 
 extern "C" int dibs_engine_step_update(dibs_engine* e, int32_t t, const void* recv_dev) {
   if (!e || !recv_dev) return fail("null argument");
+  if (e->f64) return fail("float64 engine: dibs_engine_step_update is not supported (dibs_engine_run only)");
   if (e->B > 1) return fail("batched engine: only dibs_engine_run steps it");
   HIP_OK(hipSetDevice(e->cfg.device_id));
   return step_update(e, t, packed_source(e, (const float*)recv_dev));
@@ -1762,6 +1993,7 @@ extern "C" int dibs_engine_step_update(dibs_engine* e, int32_t t, const void* re
 extern "C" int dibs_engine_eval_gradients(dibs_engine* e, int32_t t, const uint32_t* keys_theta, const uint32_t* keys_lik, const uint32_t* keys_prior,
                                           float* grad_z_lik, float* baseline_out, float* grad_theta, float* grad_z_prior) {
   if (!e) return fail("null engine");
+  if (e->f64) return fail("float64 engine: dibs_engine_eval_gradients is not supported (dibs_engine_run only)");
   if (e->B > 1) return fail("batched engine: dibs_engine_eval_gradients is not supported");
   if (!e->has_data) return fail("dibs_engine_set_data has not been called");
   const dibs_config& c = e->cfg;
@@ -2121,6 +2353,7 @@ static int agree_on_error(dibs_engine* e, unsigned int mine, unsigned int* any) 
 // A flag time-out on ANY rank (see latch_flags) makes ALL ranks repeat the chunk on events from their chunk-start copies of the carry.
 extern "C" int dibs_engine_run_sharded(dibs_engine* e, int32_t t_start, int32_t n_steps, int32_t overlapped) {
   if (!e) return fail("null engine");
+  if (e->f64) return fail("float64 engine: dibs_engine_run_sharded is not supported (dibs_engine_run only)");
   if (e->B > 1) return fail("batched engine: a batch is not sharded over ranks");
   if (!e->has_data) return fail("dibs_engine_set_data has not been called");
   if (e->n_comms < 1) return fail("dibs_engine_comm_init has not been called");
@@ -2149,6 +2382,7 @@ extern "C" int dibs_engine_run_sharded(dibs_engine* e, int32_t t_start, int32_t 
 // overlapped runs already hold them in plane 0; otherwise one all-gather of the values.
 extern "C" int dibs_engine_gather_particles(dibs_engine* e, float* z_all, float* theta_all) {
   if (!e) return fail("null engine");
+  if (e->f64) return fail("float64 engine: dibs_engine_gather_particles is not supported (dibs_engine_run only)");
   if (e->n_comms < 1) return fail("dibs_engine_comm_init has not been called");
   if (e->loopback) return fail("loopback communicator (timing only): there are no other ranks to gather from");
   HIP_OK(hipSetDevice(e->cfg.device_id));
@@ -2200,6 +2434,22 @@ struct BufInfo {
 };
 static BufInfo buf_info(const dibs_engine* e, int which) {
   const int64_t Ml = e->Mloc, dd = (int64_t)e->d * e->d;
+  if (const F64State* f = e->f64) {  // float64 engine: the float buffers in double (NODE_SCORES / PARENT_MASKS as below)
+    switch (which) {
+      case DIBS_BUF_Z: return {f->z, Ml * e->D * 8};
+      case DIBS_BUF_V_Z: return {f->vz, Ml * e->D * 8};
+      case DIBS_BUF_SCORES: return {f->scores, Ml * dd * 8};
+      case DIBS_BUF_LOGPROBS_Z: return {f->logprobs, Ml * e->S * 8};
+      case DIBS_BUF_W_LIK: return {f->w_lik, Ml * dd * 8};
+      case DIBS_BUF_W_ACYC: return {f->w_acyc, Ml * dd * 8};
+      case DIBS_BUF_GRAD_Z: return {f->gradz, Ml * e->D * 8};
+      case DIBS_BUF_KXX: return {f->kxx, Ml * e->M * 8};
+      case DIBS_BUF_PHI_Z: return {f->phi, Ml * e->D * 8};
+      case DIBS_BUF_BASELINE: return {f->baseline, Ml * 8};
+      case DIBS_BUF_NODE_SCORES: case DIBS_BUF_PARENT_MASKS: break;
+      default: return {nullptr, -1};  // (theta, packed and gathered rows: the f32 engine's, which a float64 engine does not have)
+    }
+  }
   switch (which) {
     case DIBS_BUF_Z: return {e->z, Ml * e->D * 4};
     case DIBS_BUF_V_Z: return {e->vz, Ml * e->D * 4};
@@ -2230,10 +2480,10 @@ extern "C" int dibs_engine_read_buffer(dibs_engine* e, int32_t which, void* host
   HIP_OK(hipSetDevice(e->cfg.device_id));
   HIP_OK(hipStreamSynchronize(e->stream));
   const BufInfo bi = buf_info(e, which);
-  if (bi.bytes < 0) return fail("unknown buffer id");
+  if (bi.bytes < 0) return fail(e->f64 ? "float64 engine: no such buffer (theta / packed / gathered rows belong to the float32 engine)" : "unknown buffer id");
   if (bi.bytes != nbytes) return fail("buffer size mismatch: expected " + std::to_string(bi.bytes) + " bytes");
   if (nbytes == 0) return 0;
-  if (which == DIBS_BUF_GRAD_Z || which == DIBS_BUF_GRAD_THETA) {  // strided rows of the packed buffer (single-rank engine buffer)
+  if (!e->f64 && (which == DIBS_BUF_GRAD_Z || which == DIBS_BUF_GRAD_THETA)) {  // strided rows of the packed buffer (single-rank engine buffer)
     const size_t off = which == DIBS_BUF_GRAD_Z ? (size_t)e->D : (size_t)(2 * e->D + e->P);
     const size_t w = which == DIBS_BUF_GRAD_Z ? (size_t)e->D * 4 : (size_t)e->P * 4;
     HIP_OK(hipMemcpy2D(host, w, e->pack + (size_t)e->m0 * e->E + off, (size_t)e->E * 4, w, e->Mloc, hipMemcpyDeviceToHost));
@@ -2301,6 +2551,7 @@ struct JointWorkGuard {
 extern "C" int dibs_score_graphs(dibs_engine* e, const int32_t* g, const float* theta, int32_t n, const float* x_ho,
                                  const int32_t* mask_ho, int32_t n_ho, float* out) {
   if (!e || !g || !x_ho || !out) return fail("null argument");
+  if (e->f64) return fail("float64 engine: dibs_score_graphs is not supported (dibs_engine_run only)");
   if (e->B > 1) return fail("batched engine: dibs_score_graphs is not supported (score with a standalone engine)");
   if (n <= 0) return 0;
   HIP_OK(hipSetDevice(e->cfg.device_id));
@@ -2376,5 +2627,102 @@ extern "C" int dibs_score_graphs(dibs_engine* e, const int32_t* g, const float* 
   }
   HIP_OK(hipGetLastError());
   HIP_OK(hipMemcpy(out, d_out.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ---- float64 engine: data, state, precision (include/dibs_hip.h) ----------------------------------------------------------------------
+extern "C" int dibs_engine_precision(const dibs_engine* e) { return !e ? -1 : (e->f64 ? 64 : 32); }
+
+// BGe statistics of the data in double, the oracle's bge_prepare (linearGaussian.py:78-94) to the letter; never rounded to float
+extern "C" int dibs_engine_set_data_f64(dibs_engine* e, const double* x, const int32_t* interv_mask, const double* bge_mean_obs) {
+  if (!e || !x) return fail("null argument");
+  if (!e->f64) return fail("dibs_engine_set_data_f64: not a float64 engine (dibs_config.reserved_i[1] = 64)");
+  HIP_OK(hipSetDevice(e->cfg.device_id));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  e->has_data = false;
+  F64State& f = *e->f64;
+  const dibs_config& c = e->cfg;
+  const int d = e->d, N = e->N;
+  const double amu = c.bge_alpha_mu, al = c.bge_alpha_lambd > 0 ? c.bge_alpha_lambd : d + 2.0;
+  if (!(al > d + 1)) return fail("BGe: alpha_lambd must be > n_vars + 1");  // linearGaussian.py:47
+  const double small_t = amu * (al - d - 1) / (amu + 1);
+  bool any = false;
+  if (interv_mask)
+    for (int64_t i = 0; i < (int64_t)N * d; ++i) any |= interv_mask[i] != 0;
+  const int n_mats = any ? d : 1;
+  std::vector<double> R((size_t)n_mats * d * d), Nj(d), gam((size_t)d * (d + 1)), xb(d);
+  for (int jm = 0; jm < n_mats; ++jm) {
+    auto used = [&](int n) { return !(any && interv_mask[(int64_t)n * d + jm]); };
+    double Nn = 0;
+    for (int n = 0; n < N; ++n) Nn += used(n) ? 1.0 : 0.0;
+    for (int a = 0; a < d; ++a) {
+      double s = 0;
+      for (int n = 0; n < N; ++n)
+        if (used(n)) s += x[(int64_t)n * d + a];
+      xb[a] = Nn > 0 ? s / Nn : 0.0;
+    }
+    for (int a = 0; a < d; ++a)
+      for (int b = 0; b < d; ++b) {
+        double s = 0;
+        for (int n = 0; n < N; ++n)
+          if (used(n)) s += (x[(int64_t)n * d + a] - xb[a]) * (x[(int64_t)n * d + b] - xb[b]);
+        const double ma = bge_mean_obs ? bge_mean_obs[a] : 0.0, mb = bge_mean_obs ? bge_mean_obs[b] : 0.0;
+        R[(size_t)jm * d * d + (size_t)a * d + b] = (a == b ? small_t : 0.0) + s + (Nn * amu / (Nn + amu)) * (xb[a] - ma) * (xb[b] - mb);
+      }
+    if (any) Nj[jm] = Nn;
+    else
+      for (int j = 0; j < d; ++j) Nj[j] = Nn;
+  }
+  for (int j = 0; j < d; ++j)
+    for (int l = 0; l <= d; ++l) {
+      const double Nn = Nj[j];
+      gam[(size_t)j * (d + 1) + l] = 0.5 * (log(amu) - log(Nn + amu)) + lgamma(0.5 * (Nn + al - d + l + 1)) - lgamma(0.5 * (al - d + l + 1)) -
+                                     0.5 * Nn * log(M_PI) + 0.5 * (al - d + 2 * l + 1) * log(small_t);
+    }
+  void* old[] = {f.R, f.Nj, f.gam};
+  for (void* p_ : old)
+    if (p_) hipFree(p_);
+  f.R = f.Nj = f.gam = nullptr;
+  HIP_OK(dalloc(&f.R, R.size()));
+  HIP_OK(dalloc(&f.Nj, Nj.size()));
+  HIP_OK(dalloc(&f.gam, gam.size()));
+  HIP_OK(hipMemcpy(f.R, R.data(), R.size() * 8, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(f.Nj, Nj.data(), Nj.size() * 8, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(f.gam, gam.data(), gam.size() * 8, hipMemcpyHostToDevice));
+  f.alpha_lambd = al;
+  f.n_mats = n_mats;
+  e->has_data = true;
+  return 0;
+}
+
+extern "C" int dibs_engine_set_state_f64(dibs_engine* e, const double* z, const double* v_z, const double* theta, const double* v_theta,
+                                         const uint32_t* key, const double* baseline) {
+  if (!e) return fail("null engine");
+  if (!e->f64) return fail("dibs_engine_set_state_f64: not a float64 engine (dibs_config.reserved_i[1] = 64)");
+  if (theta || v_theta) return fail("float64 engine: theta / v_theta must be null (MarginalDiBS has no parameters)");
+  HIP_OK(hipSetDevice(e->cfg.device_id));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  const size_t nz = (size_t)e->Mloc * e->D * 8;
+  if (z) HIP_OK(hipMemcpy(e->f64->z, z, nz, hipMemcpyHostToDevice));
+  if (v_z) HIP_OK(hipMemcpy(e->f64->vz, v_z, nz, hipMemcpyHostToDevice));
+  if (key) e->key = Key2{key[0], key[1]};
+  if (baseline) HIP_OK(hipMemcpy(e->f64->baseline, baseline, (size_t)e->Mloc * 8, hipMemcpyHostToDevice));
+  return 0;
+}
+
+extern "C" int dibs_engine_get_state_f64(dibs_engine* e, double* z, double* v_z, double* theta, double* v_theta, uint32_t* key, double* baseline) {
+  if (!e) return fail("null engine");
+  if (!e->f64) return fail("dibs_engine_get_state_f64: not a float64 engine (dibs_config.reserved_i[1] = 64)");
+  if (theta || v_theta) return fail("float64 engine: theta / v_theta must be null (MarginalDiBS has no parameters)");
+  HIP_OK(hipSetDevice(e->cfg.device_id));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  const size_t nz = (size_t)e->Mloc * e->D * 8;
+  if (z) HIP_OK(hipMemcpy(z, e->f64->z, nz, hipMemcpyDeviceToHost));
+  if (v_z) HIP_OK(hipMemcpy(v_z, e->f64->vz, nz, hipMemcpyDeviceToHost));
+  if (key) {
+    key[0] = e->key.a;
+    key[1] = e->key.b;
+  }
+  if (baseline) HIP_OK(hipMemcpy(baseline, e->f64->baseline, (size_t)e->Mloc * 8, hipMemcpyDeviceToHost));
   return 0;
 }

@@ -44,3 +44,29 @@ bool acyc_power_takes_events(const AcycLaunch& a);
 void acyc_launch_power(const AcycLaunch& a);   // matrix powers -> per-block partial sums (n_vars > 112: everything, straight into w_acyc)
 void acyc_launch_reduce(const AcycLaunch& a);  // partial sums -> w_acyc (same stream)
 size_t acyc_big_elems(int Mloc, int d, int Sa);
+
+// ---- tu_f64.hip: the float64 engine (kernels_f64.h; include/dibs_hip.h, dibs_config.reserved_i[1] = 64) -----------------------------
+// Everything one step of the f64 engine reads and writes; the per-step fields (alpha .. carry_prior) are set by engine.hip::step_f64.
+struct F64Args {
+  int d, k, M, S, Sa, dpad, L, tiny, prior, opt, n_mats;
+  int64_t D;
+  double alpha, beta, tau, er_c, inv_sig2, sfb, h, scale, step, alpha_lambd;
+  Key2 carry_lik, carry_prior;
+  double *z, *vz, *baseline, *scores, *probs, *w_lik, *w_acyc, *part, *logprobs, *gradz, *kxx, *phi;
+  uint32_t* thr;
+  uint64_t* masks;       // [M][d][S] (one word per parent set: n_vars <= 64)
+  double* node_scores;   // [M][d][S]
+  const double *R, *Nj, *gam;  // BGe statistics in double: R [n_mats][d][d], N_j [d], log_gamma_term [d][d + 1]
+  const float* ltab;           // [2^23] logistic value of the f32 uniform (bits >> 9) (engine.hip: f64_logistic_table)
+};
+__host__ __device__ inline size_t f64_bge_wave_bytes(int d) { return (size_t)d * 64 * 8 + 64 * 4; }
+__host__ __device__ inline size_t f64_acyc_lds_bytes(int dpad) { return (size_t)3 * dpad * (dpad + 1) * 8; }
+void f64_launch_edge(hipStream_t st, const F64Args& a);
+void f64_launch_bge(hipStream_t st, const F64Args& a);
+void f64_launch_weights(hipStream_t st, const F64Args& a);
+void f64_launch_acyc(hipStream_t st, const F64Args& a);
+void f64_launch_acyc_reduce(hipStream_t st, const F64Args& a);
+void f64_launch_grad(hipStream_t st, const F64Args& a);
+void f64_launch_kmat(hipStream_t st, const F64Args& a);
+void f64_launch_phi(hipStream_t st, const F64Args& a);
+void f64_launch_update(hipStream_t st, const F64Args& a);

@@ -187,11 +187,17 @@ def init_native_comm(engine, group=None, n_comms=2):
     engine.comm_init(box[0])
 
 
+def _no_float64(dibs, what):
+    if getattr(dibs, "precision", "float32") == "float64":
+        raise NotImplementedError(f"{what}: the float64 engine runs on one rank only (include/dibs_hip.h); use sample()")
+
+
 def sample_sharded_native(dibs, *, key, n_particles, steps, n_dim_particles=None, callback_every=None, callback=None, group=None,
                           overlapped=True):
     """``sample`` with the particles sharded over the ranks of ``group`` and the whole step loop, collectives included, inside the engine
     (``dibs_engine_run_sharded``: ncclAllGather on the engine's own streams).  Every rank calls it with the same arguments and gets
     the full result (all particles)."""
+    _no_float64(dibs, "sample_sharded_native")
     import torch
     import torch.distributed as dist
     from . import random
@@ -226,6 +232,7 @@ def sample_sharded(dibs, *, key, n_particles, steps, n_dim_particles=None, callb
     """``MarginalDiBS.sample`` / ``JointDiBS.sample`` with the particles sharded over the ranks of ``group``, the step loop driven from
     Python with torch.distributed collectives (the harness the in-engine loop of ``sample_sharded_native`` is checked against).
     Every rank calls it with the same arguments and gets the full result (all particles)."""
+    _no_float64(dibs, "sample_sharded")
     import torch
     import torch.distributed as dist
     from . import random

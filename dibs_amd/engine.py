@@ -6,6 +6,8 @@ from . import _lib
 from ._abi import BUF, K_COUNT, KERNELS, DibsConfig
 
 _BUF_DTYPE = {"NODE_SCORES": np.float64, "PARENT_MASKS": np.uint64}
+# the buffers a float64 engine (include/dibs_hip.h, dibs_config.reserved_i[1] = 64) holds in double
+_F64_BUFS = ("Z", "V_Z", "SCORES", "LOGPROBS_Z", "W_LIK", "W_ACYC", "GRAD_Z", "KXX", "PHI_Z", "BASELINE")
 
 
 def _ptr(a):
@@ -26,6 +28,8 @@ class Engine:
         self.B = max(int(cfg.reserved_i[0]), 1)   # problems of a batched engine (include/dibs_hip.h): rows [B * M], problem-major
         self.Mloc = self.B * cfg.n_particles if self.B > 1 else cfg.n_particles // cfg.n_ranks
         self.P = int(self.lib.dibs_engine_theta_size(self._h))
+        self.precision = int(self.lib.dibs_engine_precision(self._h))   # 32 or 64: the float64 engine takes and returns double arrays
+        self.dtype = np.float64 if self.precision == 64 else np.float32
         self.state_gen = 0   # bumped whenever the particles are replaced from outside (init_particles / set_state): the overlapped
                              # exchange of dibs_amd.distributed compares it with the generation its gathered values belong to
 
@@ -41,11 +45,12 @@ class Engine:
             pass
 
     def set_data(self, x, interv_mask=None, bge_mean_obs=None):
-        x = np.ascontiguousarray(x, np.float32)
+        x = np.ascontiguousarray(x, self.dtype)
         assert x.shape == (self.cfg.n_observations, self.d), x.shape
         m = None if interv_mask is None else np.ascontiguousarray(interv_mask, np.int32)
-        mo = None if bge_mean_obs is None else np.ascontiguousarray(bge_mean_obs, np.float32)
-        _lib.check(self.lib.dibs_engine_set_data(self._h, _ptr(x), _ptr(m), _ptr(mo)))
+        mo = None if bge_mean_obs is None else np.ascontiguousarray(bge_mean_obs, self.dtype)
+        f = self.lib.dibs_engine_set_data_f64 if self.precision == 64 else self.lib.dibs_engine_set_data
+        _lib.check(f(self._h, _ptr(x), _ptr(m), _ptr(mo)))
 
     # batched engine (n_problems > 1): per-problem data, particles and loop-carry keys
     def set_data_problem(self, p, x, interv_mask=None, bge_mean_obs=None):
@@ -76,14 +81,19 @@ class Engine:
         self.state_gen += 1
 
     def set_state(self, z=None, v_z=None, theta=None, v_theta=None, key=None, baseline=None):
-        f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+        f = lambda a: None if a is None else np.ascontiguousarray(a, self.dtype)
         z, v_z, theta, v_theta, baseline = f(z), f(v_z), f(theta), f(v_theta), f(baseline)
         key = None if key is None else np.ascontiguousarray(key, np.uint32)
-        _lib.check(self.lib.dibs_engine_set_state(self._h, _ptr(z), _ptr(v_z), _ptr(theta), _ptr(v_theta), _ptr(key),
-                                                  _ptr(baseline)))
+        fn = self.lib.dibs_engine_set_state_f64 if self.precision == 64 else self.lib.dibs_engine_set_state
+        _lib.check(fn(self._h, _ptr(z), _ptr(v_z), _ptr(theta), _ptr(v_theta), _ptr(key), _ptr(baseline)))
         self.state_gen += 1
 
     def get_state(self):
+        if self.precision == 64:
+            z = np.empty((self.Mloc, self.d, self.k, 2), np.float64)
+            v_z, key, baseline = np.empty_like(z), np.empty(2, np.uint32), np.empty(self.Mloc, np.float64)
+            _lib.check(self.lib.dibs_engine_get_state_f64(self._h, _ptr(z), _ptr(v_z), None, None, _ptr(key), _ptr(baseline)))
+            return dict(z=z, v_z=v_z, theta=None, v_theta=None, key=key, baseline=baseline)
         z = np.empty((self.Mloc, self.d, self.k, 2), np.float32)
         v_z = np.empty_like(z)
         theta = np.empty((self.Mloc, self.P), np.float32) if self.P else None
@@ -205,7 +215,7 @@ class Engine:
         nbytes = int(self.lib.dibs_engine_buffer_bytes(self._h, BUF[name]))
         if nbytes < 0:
             raise KeyError(name)
-        dt = _BUF_DTYPE.get(name, np.float32)
+        dt = np.float64 if (self.precision == 64 and name in _F64_BUFS) else _BUF_DTYPE.get(name, np.float32)
         out = np.empty(nbytes // np.dtype(dt).itemsize, dt)
         _lib.check(self.lib.dibs_engine_read_buffer(self._h, BUF[name], _ptr(out), nbytes))
         return out

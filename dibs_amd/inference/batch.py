@@ -43,6 +43,8 @@ def sample_batch(models, *, keys, n_particles, steps, n_dim_particles=None, call
             raise ValueError("sample_batch: every model must be a MarginalDiBS (joint models are not batched)")
         if m.grad_estimator_z != "score":
             raise ValueError("sample_batch: only the score-function estimator is batched (grad_estimator_z='score')")
+        if getattr(m, "precision", "float32") != "float32":
+            raise ValueError("sample_batch: float64 models are not batched (the float64 engine runs one problem; use sample())")
     n_dim = n_dim_particles or models[0].n_vars
     cfgs = [m._make_config(n_particles, n_dim) for m in models]
     ref = _shared_fields(cfgs[0])

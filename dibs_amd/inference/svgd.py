@@ -32,7 +32,12 @@ class _SVGDBase(DiBS):
 
     def _init_common(self, *, x, graph_model, likelihood_model, interv_mask, kernel, kernel_param, optimizer,
                      optimizer_param, alpha_linear, beta_linear, tau, n_grad_mc_samples, n_acyclicity_mc_samples,
-                     grad_estimator_z, score_function_baseline, latent_prior_std, verbose):
+                     grad_estimator_z, score_function_baseline, latent_prior_std, verbose, precision="float32"):
+        if precision not in ("float32", "float64"):
+            raise ValueError(f"precision must be 'float32' or 'float64', got {precision!r}")
+        self.precision = precision
+        # the float64 engine takes the data as given (never rounded to float32); everything else keeps the float32 copy
+        self._x_engine = np.asarray(x, np.float64) if precision == "float64" else None
         x = np.asarray(x, np.float32)
         if interv_mask is None:
             interv_mask = np.zeros_like(x, dtype=np.int32)
@@ -76,7 +81,7 @@ class _SVGDBase(DiBS):
         if self.grad_estimator_z not in ("score", "reparam"):
             raise ValueError(f"Unknown gradient estimator `{self.grad_estimator_z}`")
         return make_config(
-            n_vars=self.n_vars, n_particles=n_particles, n_observations=self.x.shape[0], n_dim=n_dim, joint=self._joint,
+            precision=64 if self.precision == "float64" else 32, n_vars=self.n_vars, n_particles=n_particles, n_observations=self.x.shape[0], n_dim=n_dim, joint=self._joint,
             graph_prior=self.graph_model._dibs_prior, edges_per_node=getattr(self.graph_model, "n_edges_per_node", 2),
             grad_estimator_z=self.grad_estimator_z, optimizer=self.optimizer, stepsize=self.optimizer_param["stepsize"],
             alpha_linear=self.alpha_linear, beta_linear=self.beta_linear, tau=self.tau,
@@ -87,7 +92,7 @@ class _SVGDBase(DiBS):
 
     def _new_engine(self, n_particles, n_dim, stream=None, **kw):
         eng = Engine(self._make_config(n_particles, n_dim, **kw), stream=stream)
-        eng.set_data(self.x, self.interv_mask if self.interv_mask.any() else None,
+        eng.set_data(self.x if self._x_engine is None else self._x_engine, self.interv_mask if self.interv_mask.any() else None,
                      getattr(self.likelihood_model, "mean_obs", None))
         return eng
 
@@ -100,6 +105,11 @@ class _SVGDBase(DiBS):
             return np.ascontiguousarray(lm.tree_to_flat(thetas), np.float32)
         th = np.asarray(thetas, np.float32)
         return np.ascontiguousarray(th.reshape(th.shape[0], -1))
+
+    def _no_float64(self, what):
+        if self.precision == "float64":
+            raise NotImplementedError(f"{what}: not available on a float64 model (the float64 engine supports sample() only; "
+                                      "construct the model with precision='float32')")
 
     def _eval(self, zs, thetas, baselines, t, **keys):
         zs = np.ascontiguousarray(zs, np.float32)
@@ -115,6 +125,7 @@ class _SVGDBase(DiBS):
     def eltwise_log_joint_prob(self, gs, single_theta, rng=None):
         """log p(theta, D | G) (marginal model: log p(D | G)) for a batch of hard graphs ``[n, d, d]`` on the training data (dibs.py:255-269)."""
         from .scoring import score_graphs
+        self._no_float64("eltwise_log_joint_prob")
         gs = np.asarray(gs)
         th = None
         if self._joint:
@@ -126,6 +137,7 @@ class _SVGDBase(DiBS):
         """Estimator of grad_Z log p(theta, D | Z) for every particle -> (``[n_particles, d, k, 2]``, baselines ``[n_particles]``)
         (dibs.py:295-321): the score-function or the Gumbel-softmax estimator, as ``grad_estimator_z`` says, with particle m's graphs drawn
         from ``subkeys[m]`` exactly as in one SVGD step (svgd.py:245-249, 699-701)."""
+        self._no_float64("eltwise_grad_z_likelihood")
         if self.grad_estimator_z not in ("score", "reparam"):
             raise ValueError(f"Unknown gradient estimator `{self.grad_estimator_z}`")
         subkeys = np.asarray(subkeys, np.uint32)
@@ -143,6 +155,7 @@ class _SVGDBase(DiBS):
     def eltwise_grad_latent_prior(self, zs, subkeys, t):
         """grad_Z log p(Z) = -beta(t) E[grad h(G~)] - Z / sigma_z^2 + grad log p(G_alpha(Z)) for every particle (dibs.py:626-658); the
         acyclicity noise of particle m is drawn from ``subkeys[m]`` (used directly, dibs.py:595)."""
+        self._no_float64("eltwise_grad_latent_prior")
         zs = np.ascontiguousarray(zs, np.float32)
         eng = self._new_engine(zs.shape[0], zs.shape[2])
         try:
@@ -191,7 +204,14 @@ class MarginalDiBS(_SVGDBase):
     def __init__(self, *, x, graph_model, likelihood_model, interv_mask=None, kernel=AdditiveFrobeniusSEKernel,
                  kernel_param=None, optimizer="rmsprop", optimizer_param=None, alpha_linear=1.0, beta_linear=1.0, tau=1.0,
                  n_grad_mc_samples=128, n_acyclicity_mc_samples=32, grad_estimator_z="score",
-                 score_function_baseline=0.0, latent_prior_std=None, verbose=False):
+                 score_function_baseline=0.0, latent_prior_std=None, verbose=False, precision="float32"):
+        """``precision="float64"``: the float64 engine (include/dibs_hip.h) -- the data, the BGe statistics and all
+        arithmetic after the random draws in double, in the order of the f64 build of the oracle (DESIGN.md section 11 has the measured
+        agreement); ``sample()`` returns the same hard
+        graphs, ``last_state`` and callbacks carry float64 arrays.  The draws stay the float32 streams of the float32 engine: this is NOT
+        JAX's x64 stream (under JAX_ENABLE_X64, uniforms are drawn as float64 from 64 random bits).  Limits: 2 <= n_vars <= 64, at most
+        1024 particles, one rank (``eltwise_grad_*``, the held-out scorers and ``sample_sharded*`` raise NotImplementedError; ``sample_batch``
+        rejects float64 models)."""
         if kernel_param is None:
             kernel_param = {"h": 5.0}
         if optimizer_param is None:
@@ -201,11 +221,16 @@ class MarginalDiBS(_SVGDBase):
                           alpha_linear=alpha_linear, beta_linear=beta_linear, tau=tau, n_grad_mc_samples=n_grad_mc_samples,
                           n_acyclicity_mc_samples=n_acyclicity_mc_samples, grad_estimator_z=grad_estimator_z,
                           score_function_baseline=score_function_baseline, latent_prior_std=latent_prior_std,
-                          verbose=verbose)
+                          verbose=verbose, precision=precision)
         from .scoring import score_graphs
         lm = likelihood_model
-        self.eltwise_log_marginal_likelihood_observ = lambda g, x_ho: score_graphs(lm, g, None, x_ho, None)
-        self.eltwise_log_marginal_likelihood_interv = lambda g, x_ho, m_ho: score_graphs(lm, g, None, x_ho, m_ho)
+        if precision == "float64":
+            def _held_out(*_a, **_k):
+                self._no_float64("eltwise_log_marginal_likelihood (held-out scoring)")
+            self.eltwise_log_marginal_likelihood_observ = self.eltwise_log_marginal_likelihood_interv = _held_out
+        else:
+            self.eltwise_log_marginal_likelihood_observ = lambda g, x_ho: score_graphs(lm, g, None, x_ho, None)
+            self.eltwise_log_marginal_likelihood_interv = lambda g, x_ho, m_ho: score_graphs(lm, g, None, x_ho, m_ho)
 
     def sample(self, *, key, n_particles, steps, n_dim_particles=None, callback=None, callback_every=None):
         st = self._run_sample(key, n_particles, steps, n_dim_particles, callback, callback_every)

@@ -57,7 +57,8 @@ typedef struct dibs_config {
   int32_t rank;             /* particle shard: this engine owns particles                            */
   int32_t n_ranks;          /*   [rank*M/n_ranks, (rank+1)*M/n_ranks)                                */
   int32_t device_id;
-  int32_t reserved_i[5];    /* [0] n_problems: 0 / 1 = one problem; B > 1 = a batched engine (see dibs_engine_set_data_problem) */
+  int32_t reserved_i[5];    /* [0] n_problems: 0 / 1 = one problem; B > 1 = a batched engine (see dibs_engine_set_data_problem)
+                               [1] precision: 0 / 32 = float32, 64 = the float64 engine (see dibs_engine_set_data_f64) */
 
   double alpha_linear;      /* dibs.py:70 */
   double beta_linear;       /* dibs.py:71 */
@@ -230,6 +231,31 @@ int dibs_engine_set_data_problem(dibs_engine* e, int32_t p, const float* x, int3
 int dibs_engine_init_particles_batch(dibs_engine* e, const uint32_t* keys);
 int dibs_engine_get_keys(dibs_engine* e, uint32_t* keys);
 int dibs_engine_set_keys(dibs_engine* e, const uint32_t* keys);
+
+/* FLOAT64 ENGINE (no reference counterpart as such: the reference reaches double precision through JAX_ENABLE_X64,
+ * dibs/models/nonlinearGaussian.py:183-185): dibs_config.reserved_i[1] = 64 makes the engine compute what the f64 build of the oracle
+ * (oracle/dibs_oracle.c with real = double) computes.  The random draws stay the f32 streams of the f32 engine (Threefry bits, f32 uniform /
+ * normal / logistic values); everything after a draw is double: the data and the BGe statistics, scores, edge probabilities, matrix powers,
+ * node scores, softmax weights, gradients, kernel matrix, phi, z, v_z and the baselines.  A Bernoulli edge compares the f32 uniform with
+ * the edge probability rounded to float, as the oracle does, so the sampled graphs equal the f64 oracle's bit for bit.  The two draws that
+ * pass through a C-library function -- the initial normals (log1p) and the acyclicity logistic values (logf) -- take their value from the
+ * host's C library in the oracle's order (a table over the 2^23 f32 uniforms for the logistic), so they too equal the oracle's.  This is NOT JAX's
+ * x64 stream (under x64, JAX draws float64 uniforms from 64 random bits).
+ * Supported: MarginalDiBS + BGe, score-function estimator, one rank, one problem, 2 <= n_vars <= 64, n_particles <= 1024 (any prior,
+ * interventions, bge_mean_obs, baseline, optimizer, rng layout).  dibs_engine_create rejects everything else with an error that starts
+ * "float64 engine:", before any device call.  dibs_engine_run steps it; dibs_engine_read_buffer / dibs_engine_buffer_bytes give the float
+ * buffers (Z, V_Z, SCORES, LOGPROBS_Z, W_LIK, W_ACYC, GRAD_Z, KXX, PHI_Z, BASELINE) as f64 arrays, NODE_SCORES / PARENT_MASKS unchanged;
+ * the other ids (theta, packed / gathered rows) do not exist on a float64 engine (buffer_bytes -1, read_buffer fails).
+ * dibs_engine_set_data accepts f32 data (widened exactly); dibs_engine_get_state / set_state / eval_gradients / step_* / the sharded loop /
+ * gather_particles and dibs_score_graphs fail on a float64 engine (they would round).
+ *   dibs_engine_set_data_f64(e, x, mask, mean_obs)   x: f64 [N, d]; mask: i32 [N, d] or NULL; mean_obs: f64 [d] or NULL
+ *   dibs_engine_set_state_f64 / get_state_f64        as the f32 pair with double z, v_z [M, d, k, 2] and baseline [M]; theta, v_theta NULL
+ *   dibs_engine_precision(e)                         32 or 64 (-1: null handle) */
+int dibs_engine_set_data_f64(dibs_engine* e, const double* x, const int32_t* interv_mask, const double* bge_mean_obs);
+int dibs_engine_set_state_f64(dibs_engine* e, const double* z, const double* v_z, const double* theta, const double* v_theta,
+                              const uint32_t* key, const double* baseline);
+int dibs_engine_get_state_f64(dibs_engine* e, double* z, double* v_z, double* theta, double* v_theta, uint32_t* key, double* baseline);
+int dibs_engine_precision(const dibs_engine* e);
 
 /* debugging / parity: copy a device buffer to the host (nbytes must match); theta size query */
 int dibs_engine_read_buffer(dibs_engine* e, int32_t which, void* host, int64_t nbytes);
