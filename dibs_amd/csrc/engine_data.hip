@@ -1,0 +1,359 @@
+// Data of an engine (include/dibs_hip.h): BGe sufficient statistics on the host, dibs_engine_set_data / _problem / _f64, and
+// dibs_score_graphs.
+#include "engine_impl.h"
+
+// in-place inverse and log-determinant of an SPD matrix (Cholesky, double)
+static bool spd_inverse_logdet(std::vector<double>& a, int n, double* logdet) {
+  std::vector<double> L((size_t)n * n, 0.0), Li((size_t)n * n, 0.0);
+  double ld = 0;
+  for (int j = 0; j < n; ++j) {
+    double s = a[(size_t)j * n + j];
+    for (int k = 0; k < j; ++k) s -= L[(size_t)j * n + k] * L[(size_t)j * n + k];
+    if (!(s > 0.0)) return false;
+    const double dj = sqrt(s);
+    ld += 2.0 * log(dj);
+    L[(size_t)j * n + j] = dj;
+    for (int i = j + 1; i < n; ++i) {
+      double t = a[(size_t)i * n + j];
+      for (int k = 0; k < j; ++k) t -= L[(size_t)i * n + k] * L[(size_t)j * n + k];
+      L[(size_t)i * n + j] = t / dj;
+    }
+  }
+  for (int c = 0; c < n; ++c) {  // Li = L^-1 (lower), column by column
+    Li[(size_t)c * n + c] = 1.0 / L[(size_t)c * n + c];
+    for (int i = c + 1; i < n; ++i) {
+      double t = 0;
+      for (int k = c; k < i; ++k) t -= L[(size_t)i * n + k] * Li[(size_t)k * n + c];
+      Li[(size_t)i * n + c] = t / L[(size_t)i * n + i];
+    }
+  }
+  for (int i = 0; i < n; ++i)  // A^-1 = Li^T Li
+    for (int j = 0; j <= i; ++j) {
+      double t = 0;
+      for (int k = i; k < n; ++k) t += Li[(size_t)k * n + i] * Li[(size_t)k * n + j];
+      a[(size_t)i * n + j] = a[(size_t)j * n + i] = t;
+    }
+  *logdet = ld;
+  return true;
+}
+
+// The host part of bge_prepare: the statistics of one data set (n_mats = 1 without interventions, d with) in double -- R_j, N_j, the table
+// of log_gamma_term and the scalars -- from float or double observations.  The float64 engine uploads them as they are; the float32
+// engine derives its float forms from them (bge_f32_forms).
+struct BgeHost {
+  int n_mats = 1;
+  double alpha_lambd = 0, alpha_mu = 0, log_t = 0;
+  std::vector<double> R, Nj, gam;
+};
+template <typename T>
+static int bge_host_stats(BgeHost* st, const dibs_config& cfg, int d, int N, const T* x, const int32_t* mask, const T* mean_obs) {
+  const double amu = cfg.bge_alpha_mu;
+  st->alpha_lambd = cfg.bge_alpha_lambd > 0 ? cfg.bge_alpha_lambd : d + 2.0;
+  if (!(st->alpha_lambd > d + 1)) return fail("BGe: alpha_lambd must be > n_vars + 1");  // linearGaussian.py:47
+  const double small_t = amu * (st->alpha_lambd - d - 1) / (amu + 1);
+  st->alpha_mu = amu;
+  st->log_t = log(small_t);
+  bool any = false;
+  if (mask)
+    for (int64_t i = 0; i < (int64_t)N * d; ++i) any |= mask[i] != 0;
+  st->n_mats = any ? d : 1;
+  const int n_mats = st->n_mats;
+  std::vector<double>& R = st->R;
+  std::vector<double>& Nj = st->Nj;
+  std::vector<double>& gam = st->gam;
+  R.assign((size_t)n_mats * d * d, 0.0);
+  Nj.assign(d, 0.0);
+  gam.assign((size_t)d * (d + 1), 0.0);
+  std::vector<double> xb(d);
+  for (int jm = 0; jm < n_mats; ++jm) {
+    double Nn = 0;
+    for (int n = 0; n < N; ++n) Nn += (any && mask[(int64_t)n * d + jm]) ? 0.0 : 1.0;
+    for (int a = 0; a < d; ++a) {
+      double s = 0;
+      for (int n = 0; n < N; ++n)
+        if (!(any && mask[(int64_t)n * d + jm])) s += (double)x[(int64_t)n * d + a];
+      xb[a] = Nn > 0 ? s / Nn : 0.0;
+    }
+    for (int a = 0; a < d; ++a)
+      for (int b = 0; b < d; ++b) {
+        double s = 0;
+        for (int n = 0; n < N; ++n)
+          if (!(any && mask[(int64_t)n * d + jm]))
+            s += ((double)x[(int64_t)n * d + a] - xb[a]) * ((double)x[(int64_t)n * d + b] - xb[b]);
+        const double ma = mean_obs ? (double)mean_obs[a] : 0.0, mb = mean_obs ? (double)mean_obs[b] : 0.0;
+        const double v = (a == b ? small_t : 0.0) + s + (Nn * amu / (Nn + amu)) * (xb[a] - ma) * (xb[b] - mb);
+        R[(size_t)jm * d * d + (size_t)a * d + b] = v;
+      }
+    if (any) Nj[jm] = Nn;
+    else
+      for (int j = 0; j < d; ++j) Nj[j] = Nn;
+  }
+  for (int j = 0; j < d; ++j)
+    for (int l = 0; l <= d; ++l) {
+      const double Nn = Nj[j], al = st->alpha_lambd;
+      gam[(size_t)j * (d + 1) + l] = 0.5 * (log(amu) - log(Nn + amu)) + lgamma(0.5 * (Nn + al - d + l + 1)) -
+                                     lgamma(0.5 * (al - d + l + 1)) - 0.5 * Nn * log(M_PI) +
+                                     0.5 * (al - d + 2 * l + 1) * log(small_t);
+    }
+  return 0;
+}
+
+// R as float, R padded to (d + 1) x (d + 1), its inverse (padded) and log-determinant: what the f32 kernels read (kernels_bge.h)
+struct BgeHostF32 {
+  std::vector<float> R, Rp, Qp;
+  std::vector<double> ldR;
+};
+static int bge_f32_forms(BgeHostF32* f, const BgeHost& h, int d) {
+  const int n_mats = h.n_mats, dp = d + 1;
+  f->R.assign(h.R.begin(), h.R.end());
+  f->Rp.assign((size_t)n_mats * dp * dp, 0.f);
+  f->Qp.assign((size_t)n_mats * dp * dp, 0.f);
+  f->ldR.assign(n_mats, 0.0);
+  for (int jm = 0; jm < n_mats; ++jm) {
+    std::vector<double> Rd(h.R.begin() + (size_t)jm * d * d, h.R.begin() + (size_t)(jm + 1) * d * d);
+    for (int a = 0; a < d; ++a)
+      for (int b = 0; b < d; ++b) f->Rp[(size_t)jm * dp * dp + (size_t)a * dp + b] = (float)Rd[(size_t)a * d + b];
+    if (!spd_inverse_logdet(Rd, d, &f->ldR[jm])) return fail("BGe: R is not positive definite");
+    for (int a = 0; a < d; ++a)
+      for (int b = 0; b < d; ++b) f->Qp[(size_t)jm * dp * dp + (size_t)a * dp + b] = (float)Rd[(size_t)a * d + b];
+  }
+  return 0;
+}
+
+static int bge_prepare(BgeStats* st, const dibs_config& cfg, int d, int N, const float* x, const int32_t* mask, const float* mean_obs) {
+  st->release();
+  BgeHost h;
+  BgeHostF32 f;
+  if (bge_host_stats(&h, cfg, d, N, x, mask, mean_obs) || bge_f32_forms(&f, h, d)) return 1;
+  st->alpha_lambd = h.alpha_lambd;
+  st->alpha_mu = h.alpha_mu;
+  st->log_t = h.log_t;
+  st->n_mats = h.n_mats;
+  const std::vector<float> &R = f.R, &Rp = f.Rp, &Qp = f.Qp;
+  const std::vector<double> &Nj = h.Nj, &gam = h.gam, &ldR = f.ldR;
+  HIP_OK(dalloc(&st->R, R.size()));
+  // R and Q = R^-1 in one allocation: the factorisation kernel addresses a problem's matrix as a 32-bit float offset from Rp, and two
+  // separate hipMalloc blocks can lie more than 2^31 floats apart on a 288 GB device (intermittent memory faults with interventions or
+  // d > 80, where the matrices are not LDS-resident; found by tests/tools/gpu_fuzz.py)
+  HIP_OK(dalloc(&st->Rp, Rp.size() + Qp.size()));
+  st->Qp = st->Rp + Rp.size();
+  HIP_OK(dalloc(&st->gam, gam.size()));
+  HIP_OK(dalloc(&st->Nj, Nj.size()));
+  HIP_OK(dalloc(&st->ldR, ldR.size()));
+  HIP_OK(hipMemcpy(st->R, R.data(), R.size() * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(st->Rp, Rp.data(), Rp.size() * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(st->Qp, Qp.data(), Qp.size() * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(st->gam, gam.data(), gam.size() * 8, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(st->Nj, Nj.data(), Nj.size() * 8, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(st->ldR, ldR.data(), ldR.size() * 8, hipMemcpyHostToDevice));
+  return 0;
+}
+
+extern "C" int dibs_engine_set_data(dibs_engine* e, const float* x, const int32_t* interv_mask, const float* bge_mean_obs) {
+  if (!e || !x) return fail("null argument");
+  if (e->B > 1) return fail("batched engine: use dibs_engine_set_data_problem");
+  if (e->f64) {  // float64 engine: the data widened exactly
+    const size_t n = (size_t)e->N * e->d;
+    std::vector<double> x64(x, x + n), mo64;
+    if (bge_mean_obs) mo64.assign(bge_mean_obs, bge_mean_obs + e->d);
+    return dibs_engine_set_data_f64(e, x64.data(), interv_mask, bge_mean_obs ? mo64.data() : nullptr);
+  }
+  HIP_OK(hipSetDevice(e->cfg.device_id));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  e->score_cache.valid = false;  // (the BGe prior mean travels with the data)
+  e->has_data = false;  // (a failure below leaves the engine without data: the next step reports it instead of reading freed statistics)
+  const size_t n = (size_t)e->N * e->d;
+  if (e->x) hipFree(e->x);
+  if (e->mask) hipFree(e->mask);
+  e->x = nullptr;
+  e->mask = nullptr;
+  HIP_OK(dalloc(&e->x, n));
+  HIP_OK(dalloc(&e->mask, n));
+  HIP_OK(hipMemcpy(e->x, x, n * 4, hipMemcpyHostToDevice));
+  if (interv_mask) HIP_OK(hipMemcpy(e->mask, interv_mask, n * 4, hipMemcpyHostToDevice));
+  if (e->cfg.likelihood == DIBS_LIK_BGE) {
+    e->has_mean_obs = bge_mean_obs != nullptr;
+    if (bge_mean_obs) e->mean_obs.assign(bge_mean_obs, bge_mean_obs + e->d);
+    if (bge_prepare(&e->bge, e->cfg, e->d, e->N, x, interv_mask, bge_mean_obs)) return 1;
+  } else {
+    if (joint_set_data(&e->jw, x, interv_mask, e->N, e->d)) return fail("joint_set_data failed");
+    if (e->cfg.likelihood == DIBS_LIK_LINGAUSS && !joint_lin_fast_path(e->d, e->N, e->tune.lin_gram) && joint_lin_set_gram(&e->jw, x, interv_mask, e->N, e->d))
+      return fail("LinearGaussian: Gram matrices: hipMalloc failed");
+  }
+  e->has_data = true;
+  return 0;
+}
+
+// ---- batched engine: data per problem (include/dibs_hip.h, n_problems) ----------------------------------------------------
+extern "C" int dibs_engine_set_data_problem(dibs_engine* e, int32_t p, const float* x, int32_t n_obs, const int32_t* interv_mask,
+                                            const float* bge_mean_obs) {
+  if (need_batch(e)) return 1;
+  if (!x) return fail("null argument");
+  if (p < 0 || p >= e->B) return fail("problem index out of range");
+  if (n_obs < 1) return fail("n_obs must be >= 1");
+  HIP_OK(hipSetDevice(e->cfg.device_id));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  if (e->stream2) HIP_OK(hipStreamSynchronize(e->stream2));
+  const int d = e->d, dp = d + 1;
+  const size_t msz = (size_t)dp * dp;
+  BgeHost h;
+  BgeHostF32 f;
+  if (bge_host_stats(&h, e->cfg, d, n_obs, x, interv_mask, bge_mean_obs) || bge_f32_forms(&f, h, d)) return 1;
+  dibs_engine::BatchStats& b = e->bst;
+  if (b.set.empty()) {
+    b.Rp.assign((size_t)e->B * d * msz, 0.f);
+    b.Qp.assign((size_t)e->B * d * msz, 0.f);
+    b.gam.assign((size_t)e->B * d * dp, 0.0);
+    b.Nj.assign((size_t)e->B * d, 0.0);
+    b.ldR.assign((size_t)e->B * d, 0.0);
+    b.set.assign((size_t)e->B, 0);
+  }
+  b.alpha_lambd = h.alpha_lambd;
+  // problem p's rows p d .. p d + d - 1: without interventions the one matrix (and logdet) repeated for every node -- the values the
+  // standalone engine reads for every node from its single copy
+  for (int j = 0; j < d; ++j) {
+    const int jm = h.n_mats > 1 ? j : 0;
+    const size_t row = (size_t)p * d + j;
+    memcpy(&b.Rp[row * msz], &f.Rp[(size_t)jm * msz], msz * 4);
+    memcpy(&b.Qp[row * msz], &f.Qp[(size_t)jm * msz], msz * 4);
+    b.ldR[row] = f.ldR[jm];
+    b.Nj[row] = h.Nj[j];
+    memcpy(&b.gam[row * dp], &h.gam[(size_t)j * dp], (size_t)dp * 8);
+  }
+  b.set[p] = 1;
+  e->has_data = false;
+  e->score_cache.valid = false;
+  BgeStats& st = e->bge;
+  if (!st.Rp) {  // the stacked arrays, allocated once ([B d] rows; Rp and Qp in one allocation, see bge_prepare)
+    HIP_OK(dalloc(&st.Rp, 2 * b.Rp.size()));
+    st.Qp = st.Rp + b.Rp.size();
+    HIP_OK(dalloc(&st.gam, b.gam.size()));
+    HIP_OK(dalloc(&st.Nj, b.Nj.size()));
+    HIP_OK(dalloc(&st.ldR, b.ldR.size()));
+    hipDeviceSynchronize();  // (dalloc's zero fills ran on the null stream)
+  }
+  st.alpha_lambd = h.alpha_lambd;
+  st.alpha_mu = h.alpha_mu;
+  st.log_t = h.log_t;
+  st.n_mats = e->B * d;
+  const size_t r0 = (size_t)p * d;
+  HIP_OK(hipMemcpy(st.Rp + r0 * msz, &b.Rp[r0 * msz], (size_t)d * msz * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(st.Qp + r0 * msz, &b.Qp[r0 * msz], (size_t)d * msz * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(st.gam + r0 * dp, &b.gam[r0 * dp], (size_t)d * dp * 8, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(st.Nj + r0, &b.Nj[r0], (size_t)d * 8, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(st.ldR + r0, &b.ldR[r0], (size_t)d * 8, hipMemcpyHostToDevice));
+  bool all = true;
+  for (char f : b.set) all = all && f;
+  e->has_data = all;
+  return 0;
+}
+
+extern "C" int dibs_score_graphs(dibs_engine* e, const int32_t* g, const float* theta, int32_t n, const float* x_ho,
+                                 const int32_t* mask_ho, int32_t n_ho, float* out) {
+  if (!e || !g || !x_ho || !out) return fail("null argument");
+  if (e->f64) return fail("float64 engine: dibs_score_graphs is not supported (dibs_engine_run only)");
+  if (e->B > 1) return fail("batched engine: dibs_score_graphs is not supported (score with a standalone engine)");
+  if (n <= 0) return 0;
+  HIP_OK(hipSetDevice(e->cfg.device_id));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  const dibs_config& c = e->cfg;
+  const int d = e->d;
+  const size_t dd = (size_t)d * d;
+  DevBuf<float> d_out;
+  HIP_OK(d_out.alloc((size_t)n));
+  dibs_engine::ScoreCache& sc = e->score_cache;
+  const size_t n_x = (size_t)n_ho * d;
+  const bool cached = sc.matches(x_ho, mask_ho, n_x);
+  if (!cached) sc.valid = false;
+  if (c.likelihood == DIBS_LIK_BGE) {
+    BgeStats& st = sc.st;  // statistics of (x_ho, mask_ho)
+    if (!cached) {
+      if (bge_prepare(&st, c, d, n_ho, x_ho, mask_ho, e->has_mean_obs ? e->mean_obs.data() : nullptr)) return 1;
+      sc.remember(x_ho, mask_ho, n_x);
+    }
+    const int W = e->W, CH = 512;
+    DevBuf<uint64_t> d_masks;
+    DevBuf<double> d_ns;
+    DevBuf<uint4> q_list;
+    DevBuf<unsigned int> q_counts;
+    HIP_OK(d_masks.alloc((size_t)d * CH * W));
+    HIP_OK(d_ns.alloc((size_t)d * CH));
+    HIP_OK(q_list.alloc((size_t)BGE_NQ * d * CH * bge_entry_u4(W)));
+    HIP_OK(q_counts.alloc((size_t)BGE_NQ));
+    const BgeQueues sq{q_list.p, q_counts.p, (uint32_t)(d * CH)};  // scratch queues for this call
+    const BgeParams bp = st.params();
+    std::vector<uint64_t> hm((size_t)d * CH * W);
+    for (int q0 = 0; q0 < n; q0 += CH) {
+      const int S = n - q0 < CH ? n - q0 : CH;
+      std::fill(hm.begin(), hm.end(), 0ull);
+      for (int s = 0; s < S; ++s)
+        for (int i = 0; i < d; ++i)
+          for (int j = 0; j < d; ++j)
+            if (i != j && g[(size_t)(q0 + s) * dd + (size_t)i * d + j] != 0) hm[((size_t)j * S + s) * W + (i >> 6)] |= 1ull << (i & 63);
+      HIP_OK(hipMemcpy(d_masks.p, hm.data(), (size_t)d * S * W * 8, hipMemcpyHostToDevice));
+      HIP_OK(hipMemsetAsync(sq.counts, 0, BGE_NQ * sizeof(unsigned int), e->stream));
+      bge_launch_sample(false, e->stream, nullptr, d_masks.p, d_ns.p, bp, Key2{0, 0}, 0, 1, 1, d, S, W, 0, sq,
+                        KmatFuse{nullptr, nullptr, 0, 0, 0, 0.f, 0.f, nullptr, 0u});
+      bge_launch_chol(e->stream, d_ns.p, bp, sq, d, S, nullptr);
+      bge_launch_sum_nodes(e->stream, d_ns.p, d_out.p + q0, d, S);
+      HIP_OK(hipStreamSynchronize(e->stream));
+    }
+  } else if (c.likelihood == DIBS_LIK_LINGAUSS || c.likelihood == DIBS_LIK_DENSENN) {
+    if (!theta) return fail("theta required");
+    const bool nn = c.likelihood == DIBS_LIK_DENSENN;
+    struct { JointWork& jw; } jg{sc.jw};
+    if (!cached) {
+      if (joint_set_data(&jg.jw, x_ho, mask_ho, n_ho, d)) return fail("joint_set_data failed");
+      if (!nn && !joint_lin_fast_path(d, n_ho, e->tune.lin_gram) && joint_lin_set_gram(&jg.jw, x_ho, mask_ho, n_ho, d)) return fail("LinearGaussian: Gram matrices: hipMalloc failed");
+      sc.remember(x_ho, mask_ho, n_x);
+    }
+    const size_t P = nn ? (size_t)e->P : dd;
+    DevBuf<float> d_th;
+    DevBuf<int32_t> d_g;
+    HIP_OK(d_th.alloc((size_t)n * P));
+    HIP_OK(d_g.alloc((size_t)n * dd));
+    HIP_OK(hipMemcpy(d_th.p, theta, (size_t)n * P * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_g.p, g, (size_t)n * dd * 4, hipMemcpyHostToDevice));
+    if (nn) {
+      const NNParams np_ = nn_params(c);
+      if (joint_nn_score_given(jg.jw, d_th.p, d_g.p, d_out.p, n, d, n_ho, np_, P, e->stream)) return fail("DenseNonlinearGaussian: scratch area: hipMalloc failed");
+    } else {
+      joint_lin_score_given(jg.jw, d_th.p, d_g.p, d_out.p, n, d, n_ho, (float)c.lin_obs_noise, (float)c.lin_mean_edge,
+                            (float)c.lin_sig_edge, e->stream);
+    }
+    HIP_OK(hipStreamSynchronize(e->stream));
+  } else {
+    return fail("dibs_score_graphs: likelihood not supported yet");
+  }
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpy(out, d_out.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ---- float64 engine: data (include/dibs_hip.h) ----------------------------------------------------------------------
+// BGe statistics of the data in double, the oracle's bge_prepare (linearGaussian.py:78-94) to the letter; never rounded to float
+extern "C" int dibs_engine_set_data_f64(dibs_engine* e, const double* x, const int32_t* interv_mask, const double* bge_mean_obs) {
+  if (!e || !x) return fail("null argument");
+  if (!e->f64) return fail("dibs_engine_set_data_f64: not a float64 engine (dibs_config.reserved_i[1] = 64)");
+  HIP_OK(hipSetDevice(e->cfg.device_id));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  e->has_data = false;
+  F64State& f = *e->f64;
+  BgeHost h;
+  if (bge_host_stats(&h, e->cfg, e->d, e->N, x, interv_mask, bge_mean_obs)) return 1;
+  const std::vector<double> &R = h.R, &Nj = h.Nj, &gam = h.gam;
+  void* old[] = {f.R, f.Nj, f.gam};
+  for (void* p_ : old)
+    if (p_) hipFree(p_);
+  f.R = f.Nj = f.gam = nullptr;
+  HIP_OK(dalloc(&f.R, R.size()));
+  HIP_OK(dalloc(&f.Nj, Nj.size()));
+  HIP_OK(dalloc(&f.gam, gam.size()));
+  HIP_OK(hipMemcpy(f.R, R.data(), R.size() * 8, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(f.Nj, Nj.data(), Nj.size() * 8, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(f.gam, gam.data(), gam.size() * 8, hipMemcpyHostToDevice));
+  f.alpha_lambd = h.alpha_lambd;
+  f.n_mats = h.n_mats;
+  e->has_data = true;
+  return 0;
+}

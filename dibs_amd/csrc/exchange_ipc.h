@@ -64,6 +64,7 @@ struct IpcComm {
   size_t set_off(int p) const { return IPC_FLAG_BYTES + (2 * pack_elems + (size_t)p * set_elems) * 4; }
 };
 
+#ifdef DIBS_TU_COMM  // the kernels are compiled in engine_comm.hip only; every other file gets the structs
 // rows src[0 .. n4) (float4) -> byte offset dst_off of every destination arena; grid = (blocks, n_dst), block = 256.
 // dst_first = 1: every rank but `me` (the rows are already in place in the own arena); 0: all ranks, own arena included (values from vsend)
 __global__ __launch_bounds__(256) void k_ipc_push(IpcPeers P, int me, int n_ranks, int include_self, const float4* __restrict__ src, size_t dst_off,
@@ -99,3 +100,4 @@ __global__ void k_ipc_signal_wait(IpcPeers P, int me, int n_ranks, int channel, 
     }
   }
 }
+#endif  // DIBS_TU_COMM

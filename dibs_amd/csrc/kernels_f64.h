@@ -2,12 +2,12 @@
 // Every quantity after a random draw is a double and every operation is the one the f64 build of oracle/dibs_oracle.c performs, in the same
 // order, without contraction (the pragma below; tu_f64.hip is also compiled with -ffp-contract=off).  The draws themselves are the f32
 // streams of rng.h: a Bernoulli edge compares the f32 uniform with the edge probability rounded to float (the `thr` test of the f32 engine),
-// the acyclicity noise is the f32 logistic value of the oracle's C-library logf (a table over the 2^23 f32 uniforms, engine.hip:
+// the acyclicity noise is the f32 logistic value of the oracle's C-library logf (a table over the 2^23 f32 uniforms, engine_f64.hip:
 // f64_logistic_table) widened to double.  Only the matrix products of the acyclicity term differ in rounding from the oracle
 // (v_mfma_f64_16x16x4_f64 accumulates with fused multiply-adds in its own order).
 //   reference: dibs/inference/dibs.py:102-184, 325-391, 557-658; dibs/models/linearGaussian.py:63-118; dibs/graph_utils.py:8-28;
 //              dibs/kernel.py:20-30; dibs/inference/svgd.py:165-267
-// Launches of one step (engine.hip, step_f64): k64_edge | k64_bge -> k64_weights (main stream) beside k64_acyc -> k64_acyc_reduce ->
+// Launches of one step (engine_f64.hip, step_f64): k64_edge | k64_bge -> k64_weights (main stream) beside k64_acyc -> k64_acyc_reduce ->
 // k64_kmat (second stream), then k64_grad -> k64_phi -> k64_update.
 #pragma once
 #include "common.h"

@@ -1,6 +1,9 @@
 // HIP kernels (gfx950) for the MarginalDiBS + BGe SVGD step.  One step = the launches listed in
-// engine.hip::step_local / step_update; DESIGN.md has the per-kernel roofline and byte counts.
+// engine_step.hip::step_local / step_update; DESIGN.md has the per-kernel roofline and byte counts.
 #pragma once
+#ifndef DIBS_TU_STEP
+#error "kernels_marginal.h defines kernels that are not templates: it is compiled in engine_step.hip only"
+#endif
 #include "common.h"
 
 #include "kernels_kmat.h"

@@ -82,6 +82,7 @@ __device__ __forceinline__ void tail_join_wait(const TailArgs& A) {
 __device__ __forceinline__ float tail_ld_joined(const TailArgs& A, const float* p) {
   return A.join_flag ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
 }
+#ifdef DIBS_TU_STEP  // the kernels of this header are compiled in engine_step.hip only; every other file gets the structs and LDS sizes
 // Do kernels of two streams really run side by side here?  Counter collection (rocprofv3 --pmc), AMD_SERIALIZE_KERNEL and debuggers run ONE
 // dispatch at a time in submission order: a consumer that polls for a flag of a kernel queued behind it would then spin until its time-out.
 // The engine asks once per process: k_probe_wait on the main stream (spins up to 2 ms), k_probe_set on the second stream behind it.
@@ -112,6 +113,7 @@ __global__ void k_wait_flag(const unsigned int* flag, unsigned int seq, unsigned
 // (RELAXED: the end of the kernel in front of this one has already released its stores; a release here would write the L2 back once more --
 //  the one-thread kernel took 4.4 us with it)
 __global__ void k_join_flag(unsigned int* flag, unsigned int seq) { __hip_atomic_store(flag, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+#endif  // DIBS_TU_STEP
 
 __host__ __device__ inline int tail_nsplit(int S, int d) {
   int n = TAIL_NT / (S > 0 ? S : 1);
@@ -145,6 +147,7 @@ __host__ inline size_t tail_lds_bytes(int d, int ldz, int S, int W, bool lik, in
   return tail_fixed_bytes(d, ldz, S, lik) + (lik ? (size_t)stage_cap * d * W * 8 : 0);
 }
 
+#ifdef DIBS_TU_STEP
 __global__ __launch_bounds__(TAIL_NT) void k_particle_grad(TailArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   if (A.kt.x != nullptr && (int)blockIdx.x >= A.n_part) {  // (block-uniform)
@@ -499,6 +502,8 @@ __global__ __launch_bounds__(TAIL_NT) void k_particle_grad(TailArgs A) {
     for (int u = 1; u < 5; ++u) atomicAdd(A.dbg + u, ts[u] - ts[u - 1]);
 }
 
+#endif  // DIBS_TU_STEP
+
 // ------------------------------------------------------------------------------------------------
 // K7c  phase C of k_particle_grad for sizes whose W, U, V do not fit in one block's LDS: grad = [W V, W^T U] - z / sigma^2 from W in
 //      global memory (k_particle_grad with w_tot), one block per (particle, 16 rows of the result, 32 latent columns):
@@ -511,6 +516,7 @@ __host__ __device__ inline size_t backproject_big_lds(int d) {
   const size_t kp4 = (size_t)((d + 3) & ~3);
   return (16 * (kp4 + 2) + kp4 * 18 + 2 * kp4 * BPB_LDQ) * 4;
 }
+#ifdef DIBS_TU_STEP
 __global__ __launch_bounds__(256) void k_backproject_big(const float* __restrict__ w_tot, const float* __restrict__ z, float* __restrict__ pack,
                                                          size_t pack_stride, int copy_z, int m0, int d, int k, float inv_sig2) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -567,3 +573,4 @@ __global__ __launch_bounds__(256) void k_backproject_big(const float* __restrict
     }
   }
 }
+#endif  // DIBS_TU_STEP

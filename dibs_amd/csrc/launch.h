@@ -1,5 +1,5 @@
 // Host-side launchers of the kernel families that live in their own translation units (tu_*.hip): plain arguments, no templates,
-// so engine.hip does not instantiate those kernels.
+// so the engine's files (engine*.hip) do not instantiate those kernels.
 #pragma once
 #include "common.h"
 #include "kernels_kmat.h"
@@ -46,7 +46,7 @@ void acyc_launch_reduce(const AcycLaunch& a);  // partial sums -> w_acyc (same s
 size_t acyc_big_elems(int Mloc, int d, int Sa);
 
 // ---- tu_f64.hip: the float64 engine (kernels_f64.h; include/dibs_hip.h, dibs_config.reserved_i[1] = 64) -----------------------------
-// Everything one step of the f64 engine reads and writes; the per-step fields (alpha .. carry_prior) are set by engine.hip::step_f64.
+// Everything one step of the f64 engine reads and writes; the per-step fields (alpha .. carry_prior) are set by engine_f64.hip::step_f64.
 struct F64Args {
   int d, k, M, S, Sa, dpad, L, tiny, prior, opt, n_mats;
   int64_t D;
@@ -57,7 +57,7 @@ struct F64Args {
   uint64_t* masks;       // [M][d][S] (one word per parent set: n_vars <= 64)
   double* node_scores;   // [M][d][S]
   const double *R, *Nj, *gam;  // BGe statistics in double: R [n_mats][d][d], N_j [d], log_gamma_term [d][d + 1]
-  const float* ltab;           // [2^23] logistic value of the f32 uniform (bits >> 9) (engine.hip: f64_logistic_table)
+  const float* ltab;           // [2^23] logistic value of the f32 uniform (bits >> 9) (engine_f64.hip: f64_logistic_table)
 };
 __host__ __device__ inline size_t f64_bge_wave_bytes(int d) { return (size_t)d * 64 * 8 + 64 * 4; }
 __host__ __device__ inline size_t f64_acyc_lds_bytes(int dpad) { return (size_t)3 * dpad * (dpad + 1) * 8; }

@@ -2,7 +2,7 @@
 // Kernels stamp the 100 MHz wall clock at their first and last instruction; gaps are between those stamps (no profiler involved).
 //   A  s1: k1, k2                                      gap k1 -> k2 (same stream, nothing in between)
 //   B  s1: k1, record(ev), k2                          an event record between two kernels
-//   C  s1: k1, record(ev), k2;  s2: wait(ev), k3       the fork of engine.hip::step_local (k3 = acyclicity kernel)
+//   C  s1: k1, record(ev), k2;  s2: wait(ev), k3       the fork of engine_step.hip::step_local (k3 = acyclicity kernel)
 //   D  s1: k1 [ext launch, stopEvent = ev], k2; s2: wait(ev), k3      fork without a record packet: the event IS k1's completion signal
 //   E  s2: k3, record(evj);  s1: k1 (long), wait(evj), k2             the join of step_local, the awaited kernel long finished
 //   F  s2: k3 [ext launch, stopEvent = evj]; s1: k1, wait(evj), k2

@@ -3,7 +3,7 @@
 The engine computes what oracle/dibs_oracle.c computes with real = double: the same f32 random streams, every later operation in double in
 the oracle's order.  Initial particles, sampled graphs and PRNG keys are compared bit for bit, every stage buffer to TOL = 1e-9 relative (max-norm, rel_err),
 where the float32 engine is held to 1e-5 .. 2e-3 (test_gpu_parity.py).  (The draws that pass through a C-library function -- the initial
-normals and the acyclicity noise's logf -- are the oracle's own values: engine.hip, f64_host_normal / f64_logistic_table.)"""
+normals and the acyclicity noise's logf -- are the oracle's own values: engine_f64.hip, f64_host_normal / f64_logistic_table.)"""
 import numpy as np
 import pytest
 

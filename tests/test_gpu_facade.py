@@ -150,7 +150,7 @@ def test_native_sharded_loop_world1_is_bit_identical_to_engine_run(joint, overla
 def test_native_sharded_loop_mixed_protocols(joint):
     """An overlapped chunk followed by a packed chunk (and by plain dibs_engine_run) on ONE engine with two communicators: the packed /
     single-rank steps move the particles without touching plane 0, so the values gathered at the end of the overlapped chunk are stale
-    afterwards -- gather_particles must re-gather and the next overlapped chunk must exchange again (engine.hip: step_update clears
+    afterwards -- gather_particles must re-gather and the next overlapped chunk must exchange again (engine_step.hip: step_update clears
     vals_fresh).  Everything bit-identical to dibs_engine_run."""
     d, M = (12, 8) if joint else (50, 16)
     data, gm, lm = make_data(d, seed=1, joint=joint)
