@@ -14,7 +14,7 @@ ACT = {"relu": 0, "tanh": 1, "sigmoid": 2, "leakyrelu": 3}
 
 BUF = dict(Z=0, V_Z=1, THETA=2, V_THETA=3, SCORES=4, LOGPROBS_Z=5, W_LIK=6, W_ACYC=7, GRAD_Z=8,
            GRAD_THETA=9, KXX=10, PHI_Z=11, BASELINE=12, NODE_SCORES=13, PARENT_MASKS=14,
-           LOGPROBS_THETA=15, PHI_THETA=16, GATHER=17)
+           LOGPROBS_THETA=15, PHI_THETA=16, GATHER=17, PROBLEM_STEP=18)
 KERNELS = ["edge", "bge_nodes", "lik_weights", "acyc", "zgrad", "kmat", "phi_update", "lin_logprobs",
            "lin_grad", "nn_theta", "nn_z", "pack", "bge_big", "acyc_reduce", "particle_grad", "k15"]
 K_COUNT = 16
@@ -66,6 +66,20 @@ class DibsConfig(C.Structure):
         ("nn_sig_param", C.c_double),
         ("reserved_d", C.c_double * 6),
     ]
+
+
+# the settings a batched engine holds per problem (dibs_problem_hparams, include/dibs_hip.h), in the struct's order
+SWEEPABLE = ("alpha_linear", "beta_linear", "h_latent", "stepsize", "score_function_baseline", "latent_prior_std",
+             "graph_prior_edges_per_node")
+
+
+class ProblemHparams(C.Structure):
+    _fields_ = [(name, C.c_double) for name in SWEEPABLE]
+
+
+def problem_hparams(cfg):
+    """the per-problem settings a dibs_config carries"""
+    return ProblemHparams(**{name: float(getattr(cfg, name)) for name in SWEEPABLE})
 
 
 def make_config(*, n_vars, n_particles, n_observations, n_dim=None, joint=False, likelihood="bge",

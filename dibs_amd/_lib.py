@@ -6,7 +6,7 @@ import ctypes as C
 import os
 import subprocess
 
-from ._abi import DibsConfig
+from ._abi import DibsConfig, ProblemHparams
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("DIBS_HIP_LIB") or os.path.join(_CSRC, "_build", "libdibs_hip.so")  # env: explicit library path
@@ -23,6 +23,7 @@ EXPORTS = [
     "dibs_engine_comm_destroy", "dibs_engine_run_sharded", "dibs_engine_gather_particles", "dibs_engine_ipc_export",
     "dibs_engine_comm_init_ipc", "dibs_engine_flag_fallbacks", "dibs_engine_debug_drop_next_flag",
     "dibs_engine_set_data_problem", "dibs_engine_init_particles_batch", "dibs_engine_get_keys", "dibs_engine_set_keys",
+    "dibs_engine_set_problem_hparams", "dibs_engine_get_problem_hparams",
     "dibs_engine_set_data_f64", "dibs_engine_set_state_f64", "dibs_engine_get_state_f64", "dibs_engine_precision",
 ]
 
@@ -102,6 +103,8 @@ def load():
     lib.dibs_engine_init_particles_batch.argtypes = [vp, vp]
     lib.dibs_engine_get_keys.argtypes = [vp, vp]
     lib.dibs_engine_set_keys.argtypes = [vp, vp]
+    lib.dibs_engine_set_problem_hparams.argtypes = [vp, i32, C.POINTER(ProblemHparams)]
+    lib.dibs_engine_get_problem_hparams.argtypes = [vp, i32, C.POINTER(ProblemHparams)]
     lib.dibs_engine_set_data_f64.argtypes = [vp, vp, vp, vp]
     lib.dibs_engine_set_state_f64.argtypes = [vp] + [vp] * 6
     lib.dibs_engine_get_state_f64.argtypes = [vp] + [vp] * 6

@@ -7,6 +7,18 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// Batched engines (include/dibs_hip.h: n_problems > 1, dibs_engine_set_problem_hparams): one row per problem of what the standalone engine
+// passes to its kernels as scalar launch arguments, derived on the host by the standalone engine's own expressions and uploaded once
+// (batch_hp_commit).  alpha / beta are this step's annealed values (float)(alpha_linear * t), (float)(beta_linear * t): k_batch_keys forms
+// them in double at the head of every step.  Kernels index the table by a block-uniform problem number p = row / M: scalar loads.
+struct ProblemHP {
+  double alpha_linear, beta_linear, sf_baseline;
+  float alpha, beta;        // this step's (k_batch_keys)
+  float prior_c;            // log odds of the Erdos-Renyi edge probability (0 for the other priors)
+  float inv_sig2;           // 1 / latent_prior_std^2
+  float h, stepsize;        // kernel bandwidth, optimizer step size
+};
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -29,6 +29,12 @@ static int64_t theta_size(const dibs_config& c) {
   return 0;
 }
 
+// Batched engines: do the kernels of a step take the per-problem values from the device table?  The sizes whose kernels have table-reading
+// forms (k_edge_scores_p, k_acyc<NT> / k_acyc_hf, k_particle_grad with W, U, V in LDS); beyond them the launch arguments of the whole batch.
+static bool batch_hp_tier(const dibs_engine* e) {
+  return e->B > 1 && e->d <= 64 && e->k <= 64 && e->w_tot == nullptr && e->tune.acyc_pipe != DIBS_PIPE_BF16;
+}
+
 // Engines alive in this process.  The in-kernel flags (fork: k_wait_flag, join: tail_join_wait) are used by an engine that is ALONE in its
 // process -- the production layout, one process per GPU: its two or three streams have a hardware queue each.  Several engines in one process
 // (the single-GPU emulation of a sharded run, tests with rank engines) share hardware queues, and a polling kernel at the head of a shared
@@ -85,7 +91,7 @@ static int engine_alloc(dibs_engine* e, const dibs_config& c, void* stream) {
     e->acyc_cpb = best;
   }
   e->acyc_nblk = (e->acyc_units + e->acyc_cpb - 1) / e->acyc_cpb;
-  e->sigz = c.latent_prior_std > 0 ? (float)c.latent_prior_std : 1.0f / sqrtf((float)e->k);
+  e->sigz = latent_sigma(c.latent_prior_std, e->k);
   if (stream) {
     e->stream = (hipStream_t)stream;
     e->own_stream = false;
@@ -188,6 +194,9 @@ static int engine_alloc(dibs_engine* e, const dibs_config& c, void* stream) {
     HIP_OK(dalloc(&e->bcarry, (size_t)e->B));
     HIP_OK(dalloc(&e->bkeys_lik, (size_t)e->Mloc));
     HIP_OK(dalloc(&e->bkeys_prior, (size_t)e->Mloc));
+    HIP_OK(dalloc(&e->hp, (size_t)e->B));
+    e->hp_host.assign((size_t)e->B, dibs_problem_hparams{c.alpha_linear, c.beta_linear, c.h_latent, c.stepsize, c.score_function_baseline,
+                                                         c.latent_prior_std, c.graph_prior_edges_per_node});
   }
   // (k_phi_gemm reads whole 128-row x 32-column tiles without bounds checks: rows padded to a multiple of 128, one more tile row of slack)
   const size_t kpad = (((Ml + 127) / 128) * 128 - Ml) * e->M + 64;
@@ -231,6 +240,7 @@ static int engine_alloc(dibs_engine* e, const dibs_config& c, void* stream) {
   if (c.joint) {
     if (joint_alloc(&e->jw, e->Mloc, e->d, e->N, e->S) != 0) return fail("joint work buffers: hipMalloc failed");
   }
+  e->hp_tier = batch_hp_tier(e);
   hipDeviceSynchronize();  // the zero fills above ran on the null stream; the engine's own stream does not wait for it
   return 0;
 }
@@ -356,7 +366,7 @@ extern "C" int dibs_engine_destroy(dibs_engine* e) {
   if (e->stream2) hipStreamSynchronize(e->stream2);
   void* ptrs[] = {e->z, e->vz, e->theta, e->vtheta, e->baseline, e->baseline2, e->scores, e->probs, e->eas, e->thr, e->w_lik, e->acyc_part, e->w_acyc,
                   e->logprobs_z, e->logprobs_th, e->pack, e->kz, e->kt, e->phi_z, e->phi_th, e->counters, e->masks,
-                  e->node_scores, e->x, e->mask, e->bq.list, e->bq.counts, e->soft_ds, e->acyc_big, e->w_tot, e->join_flag, e->fork_flag, e->carry_bak, e->soft_tri, e->ksum, e->kpart, e->kmat_ctr, e->bcarry, e->bkeys_lik, e->bkeys_prior};
+                  e->node_scores, e->x, e->mask, e->bq.list, e->bq.counts, e->soft_ds, e->acyc_big, e->w_tot, e->join_flag, e->fork_flag, e->carry_bak, e->soft_tri, e->ksum, e->kpart, e->kmat_ctr, e->bcarry, e->bkeys_lik, e->bkeys_prior, e->hp};
   for (void* p : ptrs)
     if (p) hipFree(p);
   joint_free(&e->jw);
@@ -386,6 +396,7 @@ extern "C" int dibs_engine_set_state(dibs_engine* e, const float* z, const float
   if (e->B > 1 && key) return fail("batched engine: the loop-carry keys go through dibs_engine_set_keys (key must be null)");
   HIP_OK(hipSetDevice(e->cfg.device_id));
   HIP_OK(hipStreamSynchronize(e->stream));
+  if (e->B > 1 && batch_hp_commit(e)) return 1;
   const size_t nz = (size_t)e->Mloc * e->D * 4, nt = (size_t)e->Mloc * e->P * 4;
   if (z || theta) e->vals_fresh = false;
   if (z || theta) e->kmat_ext = false;  // (an externally computed kernel slab belonged to the old values: phase B computes its own unless
@@ -435,6 +446,68 @@ extern "C" int dibs_engine_set_keys(dibs_engine* e, const uint32_t* keys) {
   HIP_OK(hipSetDevice(e->cfg.device_id));
   HIP_OK(hipStreamSynchronize(e->stream));
   HIP_OK(hipMemcpy(e->bcarry, keys, (size_t)e->B * sizeof(Key2), hipMemcpyHostToDevice));
+  return 0;
+}
+
+// ---- batched engine: per-problem hyper-parameters (include/dibs_hip.h, dibs_engine_set_problem_hparams) ---------------------------------
+static dibs_config problem_config(const dibs_engine* e, const dibs_problem_hparams& h) {
+  dibs_config c = e->cfg;
+  c.alpha_linear = h.alpha_linear;
+  c.beta_linear = h.beta_linear;
+  c.h_latent = h.h_latent;
+  c.stepsize = h.stepsize;
+  c.score_function_baseline = h.score_function_baseline;
+  c.latent_prior_std = h.latent_prior_std;
+  c.graph_prior_edges_per_node = h.graph_prior_edges_per_node;
+  return c;
+}
+// the scalars the standalone engine derives on the host from a configuration (launch_tail, launch_phi_update, launch_kmat), per problem
+static ProblemHP derive_problem_hp(const dibs_engine* e, const dibs_problem_hparams& h) {
+  const dibs_config c = problem_config(e, h);
+  const float sigz = latent_sigma(c.latent_prior_std, e->k);
+  return ProblemHP{c.alpha_linear, c.beta_linear, c.score_function_baseline, 0.f, 0.f, (float)er_log_odds(c), 1.0f / (sigz * sigz),
+                   (float)c.h_latent, (float)c.stepsize};
+}
+static bool same_derived(const ProblemHP& a, const ProblemHP& b) {
+  return a.alpha_linear == b.alpha_linear && a.beta_linear == b.beta_linear && a.sf_baseline == b.sf_baseline && a.prior_c == b.prior_c &&
+         a.inv_sig2 == b.inv_sig2 && a.h == b.h && a.stepsize == b.stepsize;
+}
+
+extern "C" int dibs_engine_set_problem_hparams(dibs_engine* e, int32_t p, const dibs_problem_hparams* hp) {
+  if (!e || !hp) return fail("batched engine: dibs_engine_set_problem_hparams: null engine or argument");
+  if (e->B <= 1) return fail("batched engine: dibs_engine_set_problem_hparams needs one (dibs_config.reserved_i[0] = n_problems must be > 1)");
+  if (p < 0 || p >= e->B) return fail("batched engine: dibs_engine_set_problem_hparams: problem index out of range");
+  if (e->hp_final)
+    return fail("batched engine: dibs_engine_set_problem_hparams after the particles were initialised (init_particles_batch / set_state / run): "
+                "latent_prior_std enters the initial draw and the device table is written once");
+  const dibs_config c = problem_config(e, *hp);
+  if (c.graph_prior == DIBS_PRIOR_ER) {  // (what dibs_engine_create asks of the shared value)
+    const double pr = er_edge_prob(c);
+    if (!(pr > 0.0 && pr < 1.0)) return fail("batched engine: problem " + std::to_string(p) + ": Erdos-Renyi prior: edge probability must be in (0, 1)");
+  }
+  const dibs_problem_hparams cfg_h{e->cfg.alpha_linear, e->cfg.beta_linear, e->cfg.h_latent, e->cfg.stepsize, e->cfg.score_function_baseline,
+                                   e->cfg.latent_prior_std, e->cfg.graph_prior_edges_per_node};
+  if (!e->hp_tier && !same_derived(derive_problem_hp(e, *hp), derive_problem_hp(e, cfg_h)))
+    return fail("batched engine: problem " + std::to_string(p) + ": hyper-parameters that differ from the configuration's need n_vars <= 64 and "
+                "n_dim <= 64 (and the default acyclicity pipe); this engine's kernels take them as launch arguments of the whole batch");
+  e->hp_host[(size_t)p] = *hp;
+  return 0;
+}
+
+extern "C" int dibs_engine_get_problem_hparams(dibs_engine* e, int32_t p, dibs_problem_hparams* hp) {
+  if (!e || !hp) return fail("batched engine: dibs_engine_get_problem_hparams: null engine or argument");
+  if (e->B <= 1) return fail("batched engine: dibs_engine_get_problem_hparams needs one (dibs_config.reserved_i[0] = n_problems must be > 1)");
+  if (p < 0 || p >= e->B) return fail("batched engine: dibs_engine_get_problem_hparams: problem index out of range");
+  *hp = e->hp_host[(size_t)p];
+  return 0;
+}
+
+int batch_hp_commit(dibs_engine* e) {
+  if (e->hp_final) return 0;
+  std::vector<ProblemHP> tab((size_t)e->B);
+  for (int p = 0; p < e->B; ++p) tab[(size_t)p] = derive_problem_hp(e, e->hp_host[(size_t)p]);
+  HIP_OK(hipMemcpy(e->hp, tab.data(), tab.size() * sizeof(ProblemHP), hipMemcpyHostToDevice));
+  e->hp_final = true;
   return 0;
 }
 
@@ -521,6 +594,7 @@ extern "C" int dibs_engine_run(dibs_engine* e, int32_t t_start, int32_t n_steps)
   if (!e->has_data) return fail("dibs_engine_set_data has not been called");
   if (e->B > 1) {
     HIP_OK(hipSetDevice(e->cfg.device_id));
+    if (batch_hp_commit(e)) return 1;
     return run_chunk(e, t_start, n_steps, [e](int t) { return step_batch(e, t); });
   }
   if (e->f64) {
@@ -613,6 +687,7 @@ static BufInfo buf_info(const dibs_engine* e, int which) {
     case DIBS_BUF_GATHER: return {e->pack, (int64_t)(e->B > 1 ? e->Mloc : e->M) * e->E * 4};
     case DIBS_BUF_GRAD_Z: return {nullptr, Ml * e->D * 4};
     case DIBS_BUF_GRAD_THETA: return {nullptr, Ml * e->P * 4};
+    case DIBS_BUF_PROBLEM_STEP: return {nullptr, e->B > 1 ? (int64_t)e->B * 8 : -1};  // (alpha, beta) out of the table's rows
     default: return {nullptr, -1};
   }
 }
@@ -631,6 +706,10 @@ extern "C" int dibs_engine_read_buffer(dibs_engine* e, int32_t which, void* host
     const size_t off = which == DIBS_BUF_GRAD_Z ? (size_t)e->D : (size_t)(2 * e->D + e->P);
     const size_t w = which == DIBS_BUF_GRAD_Z ? (size_t)e->D * 4 : (size_t)e->P * 4;
     HIP_OK(hipMemcpy2D(host, w, e->pack + (size_t)e->m0 * e->E + off, (size_t)e->E * 4, w, e->Mloc, hipMemcpyDeviceToHost));
+    return 0;
+  }
+  if (which == DIBS_BUF_PROBLEM_STEP) {
+    HIP_OK(hipMemcpy2D(host, 8, (const char*)e->hp + offsetof(ProblemHP, alpha), sizeof(ProblemHP), 8, (size_t)e->B, hipMemcpyDeviceToHost));
     return 0;
   }
   if (which == DIBS_BUF_KXX && e->kt) {  // kxx = k_z + k_theta

@@ -85,6 +85,13 @@ struct dibs_engine {
   int B = 1;
   Key2* bcarry = nullptr;                             // [B] loop-carry keys, advanced on the device (k_batch_keys)
   Key2 *bkeys_lik = nullptr, *bkeys_prior = nullptr;  // [B * M] this step's per-particle keys
+  // per-problem hyper-parameters (dibs_engine_set_problem_hparams): the host values, and the device table of what the kernels take from
+  // them (ProblemHP, common.h), written ONCE by batch_hp_commit when the particles are initialised -- set_problem_hparams is refused from
+  // then on.  hp_tier: the step's kernels read the table (n_vars, n_dim <= 64 and what else batch_hp_tier asks); otherwise only the
+  // batch-only kernels do (kernel matrix, phi, keys) and the rest take the configuration's values as launch arguments, as before
+  std::vector<dibs_problem_hparams> hp_host;
+  ProblemHP* hp = nullptr;  // [B]
+  bool hp_final = false, hp_tier = false;
   struct BatchStats {                                 // host copies of the stacked BGe statistics (padded to d matrices per problem)
     std::vector<float> Rp, Qp;
     std::vector<double> gam, Nj, ldR;
@@ -319,6 +326,8 @@ inline RowSource plane_source(const dibs_engine* e, const float* planes) {
 }
 
 // ---- engine.hip ----
+int batch_hp_commit(dibs_engine* e);  // (first use of the per-problem table: derive, upload, freeze)
+inline float latent_sigma(double latent_prior_std, int k) { return latent_prior_std > 0 ? (float)latent_prior_std : 1.0f / sqrtf((float)k); }
 void latch_flags(dibs_engine* e);
 unsigned int take_join_err(dibs_engine* e);
 int join_failure(unsigned int code, const char* what);
@@ -328,6 +337,11 @@ int step_update(dibs_engine* e, int t, const RowSource& rs, float* vals_send = n
 int step_batch(dibs_engine* e, int t);
 int carry_copy(dibs_engine* e, bool restore);
 void launch_stream_probe(hipStream_t main_stream, hipStream_t second_stream, unsigned int* words);  // k_probe_wait / k_probe_set (engine_alloc)
+// ---- tu_batch.hip: the table-reading launches of step_batch (n_vars, n_dim <= 64; dibs_engine::hp_tier) ----
+void batch_launch_edge_scores(hipStream_t st, const float* z, float* scores, uint32_t* thr, float* probs, float* eas, const ProblemHP* hp, int pM,
+                              int Mloc, int d, int k, int dpad, int ldk);
+void batch_launch_tail(hipStream_t st, const TailArgs& ta, const ProblemHP* hp, int pM, int Mloc, size_t lds);
+void batch_launch_acyc_power(const AcycLaunch& a, const ProblemHP* hp, int pM);
 // ---- engine_f64.hip ----
 int f64_alloc(dibs_engine* e);
 int f64_init_particles(dibs_engine* e, Key2 isub);

@@ -53,6 +53,7 @@ extern "C" int dibs_engine_init_particles_batch(dibs_engine* e, const uint32_t* 
   if (!keys) return fail("null argument");
   HIP_OK(hipSetDevice(e->cfg.device_id));
   HIP_OK(hipStreamSynchronize(e->stream));
+  if (batch_hp_commit(e)) return 1;  // (the per-problem values are final from here on: latent_prior_std enters the draw below)
   const int L = e->cfg.rng_layout;
   std::vector<Key2> carry((size_t)e->B);
   const uint64_t n = (uint64_t)e->M * e->D;
@@ -61,7 +62,8 @@ extern "C" int dibs_engine_init_particles_batch(dibs_engine* e, const uint32_t* 
     carry[p] = rng_split_row(k0, 2, 0, L);
     const Key2 subk = rng_split_row(k0, 2, 1, L);
     const Key2 isub = rng_split_row(subk, 2, 1, L);
-    hipLaunchKernelGGL(k_init_z, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, e->z + (size_t)p * n, isub, n, (uint64_t)0, n, e->sigz, L);
+    hipLaunchKernelGGL(k_init_z, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, e->z + (size_t)p * n, isub, n, (uint64_t)0, n,
+                       latent_sigma(e->hp_host[(size_t)p].latent_prior_std, e->k), L);
   }
   HIP_OK(hipMemcpyAsync(e->bcarry, carry.data(), carry.size() * sizeof(Key2), hipMemcpyHostToDevice, e->stream));
   HIP_OK(hipMemsetAsync(e->vz, 0, (size_t)e->Mloc * e->D * 4, e->stream));
@@ -271,6 +273,17 @@ struct PhiSeg {
   float *x, *v, *phi_out;
   float h;
 };
+// bandwidth and step-size arguments of a k_phi_update launch: the scalars, or for a batched engine its per-problem table and nothing
+template <bool BATCH>
+static PhiBandwidthArg<BATCH> phi_h_arg(const dibs_engine* e, float h) {
+  if constexpr (BATCH) return e->hp;
+  else return h;
+}
+template <bool BATCH>
+static PhiStepArg<BATCH> phi_step_arg(const dibs_engine* e) {
+  if constexpr (BATCH) return 0;
+  else return (float)e->cfg.stepsize;
+}
 // k_phi_update over `rows` particles per problem (a batched engine: grid.y = problem, the BATCH instantiation, each problem exactly a
 // standalone launch); rows of all particles at pack + m * stride; vals_send / vals_stride: the overlapped exchange's copy of the new values
 static void launch_phi_update(dibs_engine* e, const float* pack, size_t stride, const PhiSeg& s, int rows, float* vals_send, size_t vals_stride) {
@@ -292,7 +305,8 @@ static void launch_phi_update(dibs_engine* e, const float* pack, size_t stride, 
   {                                                                                                                                        \
     allow_lds(k_phi_update<TA_, F_, J_, B_>, lds);                                                                                         \
     hipLaunchKernelGGL((k_phi_update<TA_, F_, J_, B_>), g, dim3(256), lds, e->stream, pack, stride, s.val_off, s.grad_off, (int)s.len, kw,  \
-                       kseg, s.is_theta, s.x, s.v, s.phi_out, e->m0, rows, e->M, s.h, (float)c.stepsize, c.optimizer == DIBS_OPT_RMSPROP,  \
+                       kseg, s.is_theta, s.x, s.v, s.phi_out, e->m0, rows, e->M, phi_h_arg<B_>(e, s.h), phi_step_arg<B_>(e),               \
+                       c.optimizer == DIBS_OPT_RMSPROP,                                                                                    \
                        (int)cols, ngroups, vals_send, vals_stride, s.is_theta ? (size_t)e->D : (size_t)0);                                 \
   }
 #define PHI_PICK(TA_)                                                                                                                      \
@@ -567,6 +581,43 @@ int carry_copy(dibs_engine* e, bool restore) {
 // rows with explicit keys (Mg = -1, rng_explicit_row) that k_batch_keys derives from the B device-resident carries; the BGe kernels look up
 // problem m / M's statistics (BATCH instantiations); the kernel matrix is block-diagonal [B * M][M] and phi sums over a problem's own block.
 // Fork / join of the second stream by events only (no flags), the kernel matrix standalone on the second stream (no fusions).
+// Hyper-parameters: per problem, from the device table e->hp (ProblemHP; dibs_engine_set_problem_hparams, by default the configuration's
+// values in every row).  k_batch_keys forms this step's alpha and beta of every problem in double, as the host does for a standalone
+// engine; the kernel matrix and phi always read the table, the edge, acyclicity and tail kernels do where they have a table-reading form
+// (e->hp_tier) and otherwise take the configuration's values as launch arguments (set_problem_hparams accepts no others there).
+// The table-reading forms of the edge, acyclicity and tail launches (e->hp_tier; kernels and launchers in tu_batch.hip): launch blocks of
+// step_batch alone, so that the blocks the standalone step shares with it stay what they were.
+static void batch_edge_scores(dibs_engine* e) {
+  KTimer tm(e, DIBS_K_EDGE, e->stream);
+  batch_launch_edge_scores(e->stream, e->z, e->scores, e->thr, e->probs, e->eas, e->hp, e->M, e->Mloc, e->d, e->k, e->dpad, e->ldk);
+}
+static void batch_acyc(dibs_engine* e, hipStream_t st, Key2 carry) {
+  const dibs_config& c = e->cfg;
+  const AcycLaunch al{st, e->scores, e->acyc_part, e->w_acyc, nullptr, carry, 0, -1, e->Mloc, e->d, e->Sa, e->acyc_cpb, e->acyc_units,
+                      e->acyc_nblk, 0.f, (float)c.tau, c.rng_layout, c.logistic_minval_tiny, nullptr, nullptr, e->eas, e->tune.acyc_pipe,
+                      e->tune.acyc_hfw_max};
+  {
+    KTimer tm(e, DIBS_K_ACYC, st);
+    batch_launch_acyc_power(al, e->hp, e->M);
+  }
+  KTimer tm(e, DIBS_K_ACYC_REDUCE, st);
+  acyc_launch_reduce(al);
+}
+// (BGe score estimator with the prior terms, W, U, V in LDS, no riders, no join flag: what step_batch asks of launch_tail)
+static void batch_tail(dibs_engine* e, const RowTarget& rt) {
+  const dibs_config& c = e->cfg;
+  KTimer tm(e, DIBS_K_TAIL);
+  const int ldz = tail_ldz(e->d, e->k, e->S, true, LDS_LIMIT - 2048);
+  const int cap = tail_stage_cap(e->d, ldz, e->S, e->W, LDS_LIMIT - 2048);
+  const size_t lds = tail_lds_bytes(e->d, ldz, e->S, e->W, true, cap);
+  // (alpha, beta, the prior constant, 1 / sigma^2 and the baseline rate: k_particle_grad_batch fills them in from the table)
+  const TailArgs ta{e->node_scores, e->masks, e->logprobs_z, e->baseline, e->baseline2, 0.0, e->bq.counts, e->S, e->W, cap, e->probs, e->w_lik,
+                    e->w_acyc, 0.f, 0.f, c.graph_prior, 0.f, e->z, rt.base, rt.stride, rt.copy_vals, 0, e->d, e->k, ldz, 0.f, nullptr, nullptr,
+                    nullptr, 0u, nullptr, e->Mloc,
+                    KmatTile{nullptr, 0, 0, 0, nullptr, 0, 0, 0, 1, 0, 0, 0, 1, 1, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr}};
+  batch_launch_tail(e->stream, ta, e->hp, e->M, e->Mloc, lds);
+}
+
 static void kmat_batch(dibs_engine* e, hipStream_t st) {
   const dibs_config& c = e->cfg;
   KTimer tm(e, DIBS_K_KMAT, st);
@@ -576,26 +627,28 @@ static void kmat_batch(dibs_engine* e, hipStream_t st) {
     const KmatTile kt{e->z, (size_t)e->D, 0, (int)e->D, nullptr, 0, e->M, e->M, nchunk, nta, nta, 1, 1, nchunk, (float)c.scale_latent,
                       (float)c.h_latent, e->kz, nullptr, nullptr, nullptr};
     dibs_allow_lds((const void*)k_kmat_tile_batch, kmat_tile_lds_bytes());
-    hipLaunchKernelGGL(k_kmat_tile_batch, dim3((unsigned)tiles, (unsigned)e->B), dim3(KT_NT), kmat_tile_lds_bytes(), st, kt);
+    hipLaunchKernelGGL(k_kmat_tile_batch, dim3((unsigned)tiles, (unsigned)e->B), dim3(KT_NT), kmat_tile_lds_bytes(), st, kt, (const ProblemHP*)e->hp);
     return;
   }
   const size_t lds = kmat_lds_bytes((size_t)e->D);
   allow_lds(k_kmat_batch, lds);
   hipLaunchKernelGGL(k_kmat_batch, dim3(e->Mloc, (e->M + KMAT_BT - 1) / KMAT_BT), dim3(256), lds, st, (const float*)e->z, (size_t)e->D, (int)e->D,
-                     e->kz, e->M, (float)c.scale_latent, (float)c.h_latent);
+                     e->kz, e->M, (float)c.scale_latent, (const ProblemHP*)e->hp);
 }
 
 int step_batch(dibs_engine* e, int t) {
   const dibs_config& c = e->cfg;
   const float alpha = (float)(c.alpha_linear * t), beta = (float)(c.beta_linear * t);
   const int L = c.rng_layout, R = e->Mloc;  // (one rank: m0 = 0)
-  hipLaunchKernelGGL(k_batch_keys, dim3(e->B), dim3(256), 0, e->stream, e->bcarry, e->bkeys_lik, e->bkeys_prior, e->M, L);
+  hipLaunchKernelGGL(k_batch_keys, dim3(e->B), dim3(256), 0, e->stream, e->bcarry, e->bkeys_lik, e->bkeys_prior, e->M, L, e->hp, t);
   const Key2 carry_lik = key_array_as_carry(e->bkeys_lik, 0), carry_prior = key_array_as_carry(e->bkeys_prior, 0);
-  launch_edge_scores(e, e->stream, alpha, EdgeFork{}, nullptr);
+  if (e->hp_tier) batch_edge_scores(e);
+  else launch_edge_scores(e, e->stream, alpha, EdgeFork{}, nullptr);
   // acyclicity term and kernel matrix on the second stream (both need only this step's z / scores), the likelihood chain on the first
   const EventFork ef(e);
   if (ef.fork()) return 1;
-  launch_acyc(e, ef.s2, carry_prior, -1, alpha);
+  if (e->hp_tier) batch_acyc(e, ef.s2, carry_prior);
+  else launch_acyc(e, ef.s2, carry_prior, -1, alpha);
   kmat_batch(e, ef.s2);
   if (ef.chain_done()) return 1;
   BgeParams bp = e->bge.params();
@@ -610,7 +663,8 @@ int step_batch(dibs_engine* e, int t) {
   }
   if (ef.join()) return 1;
   const RowTarget rt = packed_rows(e, e->pack);
-  launch_tail(e, rt, TailOpts{alpha, beta, true, true, e->w_lik, false, nullptr, false});
+  if (e->hp_tier) batch_tail(e, rt);
+  else launch_tail(e, rt, TailOpts{alpha, beta, true, true, e->w_lik, false, nullptr, false});
   std::swap(e->baseline, e->baseline2);
   {
     // SVGD transform + optimizer step: k_phi_update's BATCH instantiation, grid.y = problem, each problem exactly a standalone launch

@@ -165,9 +165,9 @@ __device__ __forceinline__ void acyc_matmul(float* __restrict__ lds, int c_off, 
 }
 
 template <int NT, bool PAIRED>
-__global__ __launch_bounds__(256) void k_acyc(const float* __restrict__ scores, float* __restrict__ part, Key2 carry, int m0,
-                                              int M_global, int d, int Sa, int cpb, float alpha, float tau, int layout,
-                                              int tiny, int n_acyc_blk) {
+__device__ __forceinline__ void acyc_block(const float* __restrict__ scores, float* __restrict__ part, Key2 carry, int m0,
+                                           int M_global, int d, int Sa, int cpb, float alpha, float tau, int layout,
+                                           int tiny, int n_acyc_blk) {
   constexpr int DP = 16 * NT, LD = DP + 4, BUF = DP * LD;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int blk = blockIdx.x, m = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -289,4 +289,17 @@ __global__ __launch_bounds__(256) void k_acyc(const float* __restrict__ scores, 
     }
   }
 }
-
+template <int NT, bool PAIRED>
+__global__ __launch_bounds__(256) void k_acyc(const float* __restrict__ scores, float* __restrict__ part, Key2 carry, int m0,
+                                              int M_global, int d, int Sa, int cpb, float alpha, float tau, int layout,
+                                              int tiny, int n_acyc_blk) {
+  acyc_block<NT, PAIRED>(scores, part, carry, m0, M_global, d, Sa, cpb, alpha, tau, layout, tiny, n_acyc_blk);
+}
+// batched engines (include/dibs_hip.h, per-problem hyper-parameters): alpha of the block's particle from row m / pM of the table
+// (block-uniform: a scalar load)
+template <int NT, bool PAIRED>
+__global__ __launch_bounds__(256) void k_acyc_batch(const float* __restrict__ scores, float* __restrict__ part, Key2 carry, int m0,
+                                                    int M_global, int d, int Sa, int cpb, const ProblemHP* __restrict__ hp, int pM,
+                                                    float tau, int layout, int tiny, int n_acyc_blk) {
+  acyc_block<NT, PAIRED>(scores, part, carry, m0, M_global, d, Sa, cpb, hp[blockIdx.y / (unsigned)pM].alpha, tau, layout, tiny, n_acyc_blk);
+}

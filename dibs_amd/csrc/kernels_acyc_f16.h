@@ -208,9 +208,9 @@ __device__ __forceinline__ float ahf_pow2(int e) { return __uint_as_float((uint3
 
 // FOUR: d > 48 (all four row / column tiles in use); the d <= 48 instantiation skips the fourth wave's products and the fourth column tile
 template <bool FOUR, int WPE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_acyc_hf(const float* __restrict__ scores, const float* __restrict__ eas, float* __restrict__ part, Key2 carry, int m0,
-                                                 int M_global, int Mloc, int d, int Sa, int cpb, float alpha, float tau, int layout,
-                                                 int tiny, int n_acyc_blk) {
+__device__ __forceinline__ void acyc_hf_block(const float* __restrict__ scores, const float* __restrict__ eas, float* __restrict__ part, Key2 carry, int m0,
+                                              int M_global, int Mloc, int d, int Sa, int cpb, float alpha, float tau, int layout,
+                                              int tiny, int n_acyc_blk) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   unsigned char* const sb = reinterpret_cast<unsigned char*>(smem);
   uint32_t* const slots = reinterpret_cast<uint32_t*>(sb + 2 * AHF_IMG_STRIDE);  // [2][4] row maxima of the waves, ping-pong
@@ -417,6 +417,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
         if (b < d) po[b] = out[tj][i];
       }
   }
+}
+template <bool FOUR, int WPE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_acyc_hf(const float* __restrict__ scores, const float* __restrict__ eas, float* __restrict__ part, Key2 carry, int m0,
+                                                 int M_global, int Mloc, int d, int Sa, int cpb, float alpha, float tau, int layout,
+                                                 int tiny, int n_acyc_blk) {
+  acyc_hf_block<FOUR, WPE>(scores, eas, part, carry, m0, M_global, Mloc, d, Sa, cpb, alpha, tau, layout, tiny, n_acyc_blk);
+}
+// batched engines (include/dibs_hip.h, per-problem hyper-parameters): alpha of the block's particle (the XCD-aware numbering of
+// acyc_hf_block) from row m / pM of the table -- block-uniform: a scalar load
+template <bool FOUR, int WPE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_acyc_hf_batch(const float* __restrict__ scores, const float* __restrict__ eas, float* __restrict__ part,
+                                                       Key2 carry, int m0, int M_global, int Mloc, int d, int Sa, int cpb,
+                                                       const ProblemHP* __restrict__ hp, int pM, float tau, int layout, int tiny, int n_acyc_blk) {
+  const int L = blockIdx.x + gridDim.x * blockIdx.y, m = ((L >> 3) / (int)gridDim.x) * 8 + (L & 7);
+  if (m >= Mloc) return;  // (the padding blocks of the grid: no row of the table)
+  acyc_hf_block<FOUR, WPE>(scores, eas, part, carry, m0, M_global, Mloc, d, Sa, cpb, hp[m / pM].alpha, tau, layout, tiny, n_acyc_blk);
 }
 
 

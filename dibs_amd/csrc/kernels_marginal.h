@@ -7,6 +7,7 @@
 #include "common.h"
 
 #include "kernels_kmat.h"
+#include "kernels_edge_p.h"
 
 // ------------------------------------------------------------------------------------------------
 // particle init: z = normal(subk, (M, d, k, 2)) * std          svgd.py:145-146 / 509-510
@@ -144,76 +145,8 @@ __global__ __launch_bounds__(1024) void k_edge_scores_p(const float* __restrict_
                                                         float* __restrict__ probs, float* __restrict__ eas, float alpha, int d, int k,
                                                         int dpad, int ldk, unsigned int* __restrict__ done_ctr,
                                                         unsigned int* __restrict__ done_flag, unsigned int done_seq) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* Us = smem;
-  float* Vs = smem + (size_t)dpad * ldk;
-  const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float2* zm = reinterpret_cast<const float2*>(z + (size_t)m * d * k * 2);
-  const int nt = dpad >> 4;
-  float2 uv[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int i = wave + 16 * r;
-    const bool in = i < d && lane < k;
-    uv[r] = zm[in ? i * k + lane : 0];
-    if (!in) uv[r] = make_float2(0.f, 0.f);
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int i = wave + 16 * r;
-    if (i < dpad) {
-      if (lane < ldk) {  // (ldk < 64 for small k: the row ends before the wave does)
-        Us[i * ldk + lane] = uv[r].x;
-        Vs[i * ldk + lane] = uv[r].y;
-      }
-      if (64 + lane < ldk) {  // (row padding beyond the 64 latent columns a wave covers: ldk = kp + (2 - kp) mod 32 <= 98)
-        Us[i * ldk + 64 + lane] = 0.f;
-        Vs[i * ldk + 64 + lane] = 0.f;
-      }
-    }
-  }
-  __syncthreads();
-  const int t = wave;
-  if (t < nt * nt) {  // (wave-uniform)
-    const int ti = t / nt, tj = t - ti * nt, kp = (k + 3) & ~3;
-    const float* ua = Us + (size_t)(ti * 16 + (lane & 15)) * ldk + (lane >> 4);
-    const float* vb = Vs + (size_t)(tj * 16 + (lane & 15)) * ldk + (lane >> 4);
-    f32x4 a = {0.f, 0.f, 0.f, 0.f};
-    for (int k0 = 0; k0 < kp; k0 += 4) a = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[k0], vb[k0], a, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = ti * 16 + (lane >> 4) * 4 + r, col = tj * 16 + (lane & 15);
-      if (row < d && col < d) {
-        const float s = a[r];
-        const size_t o = ((size_t)m * d + row) * d + col;
-        const double ex = exp(-(double)__fmul_rn(alpha, s));  // (the epilogue of k_edge_scores, operation for operation)
-        const float pf = (float)(1.0 / (1.0 + ex));
-        if (done_ctr) {  // (what the second stream reads goes out at agent scope: see below)
-          __hip_atomic_store(scores + o, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (eas) __hip_atomic_store(eas + o, (float)ex, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-          scores[o] = s;
-          if (eas) eas[o] = (float)ex;
-        }
-        if (thr) thr[o] = row == col ? 0u : (uint32_t)ceilf(pf * 8388608.0f);  // (null: the copy of the second stream, scores / eas only)
-        if (probs) probs[o] = row == col ? 0.f : pf;
-      }
-    }
-  }
-  // done_ctr != null: the fork to the engine's second stream without an event (k_wait_flag there polls done_flag): scores / eas were stored at
-  // agent scope (complete once the storing wave has waited for vmcnt(0): the barrier alone does not), every block counts itself, the last one
-  // publishes the step's sequence number
-  if (done_ctr) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0 && atomicAdd(done_ctr, 1u) == gridDim.x - 1u) {
-      atomicExch(done_ctr, 0u);  // (the next launch of this kernel is behind this one in its stream)
-      __hip_atomic_store(done_flag, done_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  edge_scores_p_block(z, scores, thr, probs, eas, alpha, d, k, dpad, ldk, done_ctr, done_flag, done_seq);
 }
-
 // the tiled kernel matrix as launches of its own (second stream of the joint / many-particle configurations): grid <= tiles * chunks, block = 1024;
 // dynamic LDS = kmat_tile_lds_bytes().  k_kmat_finish: grid = Mloc, block = 256
 __global__ __launch_bounds__(KT_NT) void k_kmat_tile(KmatTile kt) {
@@ -240,18 +173,20 @@ __global__ __launch_bounds__(256) void k_kmat(const float* __restrict__ pack, si
 // ---- batched engines (include/dibs_hip.h: n_problems = B > 1; rows [B * M], problem-major) ----
 // block-diagonal kernel matrix kout [B * M][M]: row a of problem p = a / M against the M particles of p only, by the code of the standalone
 // engine (kmat_block, symmetric: the block's upper triangle mirrored) -- bit-identical entries.  grid = (B * M, ceil(M / KMAT_BT))
+// (the bandwidth h of problem p from the per-problem table, common.h)
 __global__ __launch_bounds__(256) void k_kmat_batch(const float* __restrict__ z, size_t stride, int len, float* __restrict__ kout, int M,
-                                                    float scale, float h) {
+                                                    float scale, const ProblemHP* __restrict__ hp) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int a = blockIdx.x, p = a / M;
-  kmat_block(smem, z + (size_t)p * M * stride, stride, 0, len, kout + (size_t)p * M * M, 0, M, scale, h, 1, a - p * M, blockIdx.y);
+  kmat_block(smem, z + (size_t)p * M * stride, stride, 0, len, kout + (size_t)p * M * M, 0, M, scale, hp[p].h, 1, a - p * M, blockIdx.y);
 }
 // ... the tiled form (standalone engines from DibsTuning::kmat_tiled_min particles): blockIdx.y = problem, one piece per tile (nsplit = 1:
 // the entries do not depend on the cut, see KmatTile).  kt describes ONE problem (x, kout of problem 0)
-__global__ __launch_bounds__(KT_NT) void k_kmat_tile_batch(KmatTile kt) {
+__global__ __launch_bounds__(KT_NT) void k_kmat_tile_batch(KmatTile kt, const ProblemHP* __restrict__ hp) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const size_t p = blockIdx.y;
   KmatTile k = kt;
+  k.h = hp[p].h;
   k.x = kt.x + p * (size_t)kt.M * kt.stride;
   k.kout = kt.kout + p * (size_t)kt.M * kt.M;
   kmat_tile_block(smem, k, (int)blockIdx.x, (int)gridDim.x, (int)threadIdx.x);
@@ -259,8 +194,10 @@ __global__ __launch_bounds__(KT_NT) void k_kmat_tile_batch(KmatTile kt) {
 // per-problem keys of one step from the B device-resident loop-carry keys (svgd.py:245, 251 per problem): carry_lik = carry, particle m's
 // likelihood key = row 1 + m of split(carry_lik, M + 1), carry_prior = row 0 of it, the prior keys likewise, and the carry advances to row
 // 0 of split(carry_prior, M + 1) -- what step_local / next_carry do on the host for one problem.  grid = B, block = 256
+// This step's annealed alpha and beta of problem p go to its row of the per-problem table: (float)(alpha_linear * t) with the product in
+// double, the expression of step_local on the host (one rounding to double, one to float: nothing to contract).
 __global__ __launch_bounds__(256) void k_batch_keys(Key2* __restrict__ carry, Key2* __restrict__ keys_lik, Key2* __restrict__ keys_prior, int M,
-                                                    int layout) {
+                                                    int layout, ProblemHP* __restrict__ hp, int t) {
   const int p = blockIdx.x;
   const Key2 c_lik = carry[p];
   const uint32_t n = (uint32_t)M + 1u;
@@ -270,7 +207,11 @@ __global__ __launch_bounds__(256) void k_batch_keys(Key2* __restrict__ carry, Ke
     keys_prior[(size_t)p * M + m] = rng_split_row(c_prior, n, (uint32_t)m + 1u, layout);
   }
   __syncthreads();  // (every thread has read carry[p])
-  if (threadIdx.x == 0) carry[p] = rng_split_row(c_prior, n, 0u, layout);
+  if (threadIdx.x == 0) {
+    carry[p] = rng_split_row(c_prior, n, 0u, layout);
+    hp[p].alpha = (float)(hp[p].alpha_linear * (double)t);
+    hp[p].beta = (float)(hp[p].beta_linear * (double)t);
+  }
 }
 
 // rmsprop of jax.example_libraries.optimizers (svgd.py:117-120, 265): v <- 0.9 v + (1 - 0.9) phi^2, x <- x - step phi / sqrt(v + 1e-8).
@@ -320,12 +261,18 @@ __host__ __device__ inline size_t phi_update_lds_bytes(int TA, int M) {
 // kernel entries.  JOINT: a second kernel matrix (theta), weights ks = kz + kt and the repulsion of the segment's own kernel.
 // BATCH (batched engines, include/dibs_hip.h n_problems): blockIdx.y = problem p; its M rows of pack / x / v / phi_out and its block
 // [M][M] of the block-diagonal kernel matrix are the whole input of a standalone launch (m0 = 0, Mloc = M): the same sums in the same order.
+// bandwidth and step size of a launch: two float arguments, as ever; the BATCH instantiations take the per-problem table (common.h) in the
+// place of the first and nothing (an int that is not read) in the place of the second
+template <bool BATCH>
+using PhiBandwidthArg = std::conditional_t<BATCH, const ProblemHP*, float>;
+template <bool BATCH>
+using PhiStepArg = std::conditional_t<BATCH, int, float>;
 template <int TA, bool FULL, bool JOINT, bool BATCH = false>
 __global__ __launch_bounds__(256) void k_phi_update(const float* __restrict__ pack, size_t pack_stride, size_t val_off,
                                                     size_t grad_off, int len, const float* __restrict__ kz,
                                                     const float* __restrict__ kt, int seg_is_theta, float* __restrict__ x,
                                                     float* __restrict__ v, float* __restrict__ phi_out, int m0, int Mloc,
-                                                    int M, float h, float stepsize, int rmsprop, int ncols, int ngroups,
+                                                    int M, PhiBandwidthArg<BATCH> h_arg, PhiStepArg<BATCH> stepsize_arg, int rmsprop, int ncols, int ngroups,
                                                     float* __restrict__ vout, size_t vout_stride, size_t vout_off) {
   // 1-D grid, XCD-aware: workgroups go round-robin to the 8 XCDs, each with its own L2.  Linear id L = 8 (ngroups c_hi + g) + c_lo runs
   // the `ngroups` particle groups of column slab c = 8 c_hi + c_lo on XCD c_lo, back to back: the slab's [z_b | grad_b] rows (64 KiB) are
@@ -333,6 +280,11 @@ __global__ __launch_bounds__(256) void k_phi_update(const float* __restrict__ pa
   // packed rows 16 times per launch: 82 MB of L2 misses).
   const int L = blockIdx.x, c_lo = L & 7, tq = L >> 3, grp = tq % ngroups, bx = (tq / ngroups) * 8 + c_lo;
   if (bx >= ncols) return;  // (block-uniform)
+  float h, stepsize;
+  if constexpr (!BATCH) {
+    h = h_arg;
+    stepsize = stepsize_arg;
+  }
   if constexpr (BATCH) {
     static_assert(!JOINT, "batched engines run the marginal model only");
     const size_t p = blockIdx.y;
@@ -341,6 +293,8 @@ __global__ __launch_bounds__(256) void k_phi_update(const float* __restrict__ pa
     x += p * (size_t)M * len;
     v += p * (size_t)M * len;
     if (phi_out) phi_out += p * (size_t)M * len;
+    h = h_arg[p].h;  // (the problem's own bandwidth and step size)
+    stepsize = h_arg[p].stepsize;
   }
   typedef float f32x2 __attribute__((ext_vector_type(2)));
   extern __shared__ __attribute__((aligned(16))) float smem[];

@@ -147,8 +147,8 @@ __host__ inline size_t tail_lds_bytes(int d, int ldz, int S, int W, bool lik, in
   return tail_fixed_bytes(d, ldz, S, lik) + (lik ? (size_t)stage_cap * d * W * 8 : 0);
 }
 
-#ifdef DIBS_TU_STEP
-__global__ __launch_bounds__(TAIL_NT) void k_particle_grad(TailArgs A) {
+#if defined(DIBS_TU_STEP) || defined(DIBS_TU_BATCH)  // (tu_batch.hip: the block, under k_particle_grad_batch)
+__device__ __forceinline__ void particle_grad_block(const TailArgs& A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   if (A.kt.x != nullptr && (int)blockIdx.x >= A.n_part) {  // (block-uniform)
     kmat_tile_block(reinterpret_cast<float*>(smem_raw), A.kt, (int)blockIdx.x - A.n_part, (int)gridDim.x - A.n_part, (int)threadIdx.x);
@@ -501,8 +501,23 @@ __global__ __launch_bounds__(TAIL_NT) void k_particle_grad(TailArgs A) {
   if (A.dbg && m == 0 && tid == 0)
     for (int u = 1; u < 5; ++u) atomicAdd(A.dbg + u, ts[u] - ts[u - 1]);
 }
-
-#endif  // DIBS_TU_STEP
+#endif
+#ifdef DIBS_TU_STEP
+__global__ __launch_bounds__(TAIL_NT) void k_particle_grad(TailArgs A) { particle_grad_block(A); }
+#endif
+#ifdef DIBS_TU_BATCH
+// batched engines (include/dibs_hip.h, per-problem hyper-parameters): the same block with the five scalars of the particle's problem, row
+// m / pM of the table (block-uniform: scalar loads), in place of the launch arguments
+__global__ __launch_bounds__(TAIL_NT) void k_particle_grad_batch(TailArgs A, const ProblemHP* __restrict__ hp, int pM) {
+  const ProblemHP& h = hp[blockIdx.x / (unsigned)pM];
+  A.alpha = h.alpha;
+  A.beta = h.beta;
+  A.er_c = h.prior_c;
+  A.inv_sig2 = h.inv_sig2;
+  A.sf_baseline = h.sf_baseline;
+  particle_grad_block(A);
+}
+#endif  // DIBS_TU_BATCH
 
 // ------------------------------------------------------------------------------------------------
 // K7c  phase C of k_particle_grad for sizes whose W, U, V do not fit in one block's LDS: grad = [W V, W^T U] - z / sigma^2 from W in

@@ -3,7 +3,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._abi import BUF, K_COUNT, KERNELS, DibsConfig
+from ._abi import BUF, K_COUNT, KERNELS, SWEEPABLE, DibsConfig, ProblemHparams
 
 _BUF_DTYPE = {"NODE_SCORES": np.float64, "PARENT_MASKS": np.uint64}
 # the buffers a float64 engine (include/dibs_hip.h, dibs_config.reserved_i[1] = 64) holds in double
@@ -60,6 +60,21 @@ class Engine:
         assert m is None or m.shape == x.shape, m.shape
         mo = None if bge_mean_obs is None else np.ascontiguousarray(bge_mean_obs, np.float32)
         _lib.check(self.lib.dibs_engine_set_data_problem(self._h, int(p), _ptr(x), int(x.shape[0]), _ptr(m), _ptr(mo)))
+
+    def set_problem_hparams(self, p, hparams=None, **kw):
+        """Per-problem hyper-parameters of a batched engine (include/dibs_hip.h, dibs_engine_set_problem_hparams): a ProblemHparams, or
+        keywords out of ``_abi.SWEEPABLE`` on top of the problem's current values.  Only before the particles are initialised."""
+        hp = self.get_problem_hparams(p) if hparams is None else hparams
+        for name, v in kw.items():
+            if name not in SWEEPABLE:
+                raise TypeError(f"{name} is not a per-problem setting (one of {', '.join(SWEEPABLE)})")
+            setattr(hp, name, float(v))
+        _lib.check(self.lib.dibs_engine_set_problem_hparams(self._h, int(p), C.byref(hp)))
+
+    def get_problem_hparams(self, p):
+        hp = ProblemHparams()
+        _lib.check(self.lib.dibs_engine_get_problem_hparams(self._h, int(p), C.byref(hp)))
+        return hp
 
     def init_particles_batch(self, keys):
         keys = np.ascontiguousarray(np.asarray(keys, np.uint32).reshape(self.B, 2))

@@ -26,25 +26,34 @@ def _shared_fields(cfg):
     return out
 
 
+def _batchable(models, keys, who):
+    """What sample_batch and sample_sweep (`who`) ask of their arguments alike: as many keys as models, every model a float32 MarginalDiBS
+    with the score-function estimator.  Returns (models, keys) as lists."""
+    models = list(models)
+    keys = [random.as_key(k) for k in keys]
+    if not models:
+        return models, keys
+    if len(keys) != len(models):
+        raise ValueError(f"{who}: {len(models)} models but {len(keys)} keys")
+    for m in models:
+        if not isinstance(m, MarginalDiBS):
+            raise ValueError(f"{who}: every model must be a MarginalDiBS (joint models are not batched)")
+        if m.grad_estimator_z != "score":
+            raise ValueError(f"{who}: only the score-function estimator is batched (grad_estimator_z='score')")
+        if getattr(m, "precision", "float32") != "float32":
+            raise ValueError(f"{who}: float64 models are not batched (the float64 engine runs one problem; use sample())")
+    return models, keys
+
+
 def sample_batch(models, *, keys, n_particles, steps, n_dim_particles=None, callback=None, callback_every=None):
     """Run ``models[i].sample(key=keys[i], n_particles=..., steps=..., ...)`` for every i in one batched engine; returns the list of the
     results (hard graphs ``[n_particles, d, d]`` per problem).  Chunking, step overshoot and the callback protocol are those of
     ``sample()``: after every chunk ``callback(dibs=models[i], t=..., zs=z_i)`` is called for each i in order.  Raises ``ValueError``
     before any device work if the models are not all MarginalDiBS with the score-function estimator, or disagree on anything the batch
     shares (sizes, graph prior, hyper-parameters, BGe parameters, estimator, optimizer, kernel)."""
-    models = list(models)
-    keys = [random.as_key(k) for k in keys]
+    models, keys = _batchable(models, keys, "sample_batch")
     if not models:
         return []
-    if len(keys) != len(models):
-        raise ValueError(f"sample_batch: {len(models)} models but {len(keys)} keys")
-    for m in models:
-        if not isinstance(m, MarginalDiBS):
-            raise ValueError("sample_batch: every model must be a MarginalDiBS (joint models are not batched)")
-        if m.grad_estimator_z != "score":
-            raise ValueError("sample_batch: only the score-function estimator is batched (grad_estimator_z='score')")
-        if getattr(m, "precision", "float32") != "float32":
-            raise ValueError("sample_batch: float64 models are not batched (the float64 engine runs one problem; use sample())")
     n_dim = n_dim_particles or models[0].n_vars
     cfgs = [m._make_config(n_particles, n_dim) for m in models]
     ref = _shared_fields(cfgs[0])
@@ -58,12 +67,20 @@ def sample_batch(models, *, keys, n_particles, steps, n_dim_particles=None, call
     if B == 1:  # (a batch of one is the standalone engine)
         return [models[0].sample(key=keys[0], n_particles=n_particles, steps=steps, n_dim_particles=n_dim_particles,
                                  callback=callback, callback_every=callback_every)]
-    cfg = cfgs[0]
+    return _run_batched(models, keys, cfgs[0], n_particles, n_dim, steps, callback, callback_every)
+
+
+def _run_batched(models, keys, cfg, n_particles, n_dim, steps, callback, callback_every, hparams=None):
+    """The B problems in one batched engine created from ``cfg``; ``hparams``: per problem a ProblemHparams (sample_sweep), or None for
+    the configuration's values.  Sets every model's ``last_state`` and returns the list of hard graphs."""
+    B = len(models)
     cfg.reserved_i[0] = B
     eng = Engine(cfg)
     try:
         for i, m in enumerate(models):
             eng.set_data_problem(i, m.x, m.interv_mask if m.interv_mask.any() else None, getattr(m.likelihood_model, "mean_obs", None))
+            if hparams is not None:
+                eng.set_problem_hparams(i, hparams[i])
         eng.init_particles_batch(np.stack([np.asarray(k, np.uint32).reshape(2) for k in keys]))
         for m in models:
             if m.latent_prior_std is None:

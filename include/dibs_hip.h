@@ -104,6 +104,7 @@ enum {
   DIBS_BUF_LOGPROBS_THETA = 15, /* f32 [Mloc, S]                                   */
   DIBS_BUF_PHI_THETA = 16,
   DIBS_BUF_GATHER = 17,    /* f32 packed all-gather payload        */
+  DIBS_BUF_PROBLEM_STEP = 18, /* f32 [B, 2]  batched engines: (alpha, beta) of the last step as the device formed them per problem */
   DIBS_BUF_COUNT
 };
 
@@ -217,8 +218,8 @@ int dibs_engine_comm_init_ipc(dibs_engine* e, const void* blobs_all);
 
 /* BATCHED ENGINE (no reference counterpart; the JAX equivalent is vmap of the SVGD loop over keys and data): dibs_config.reserved_i[0] =
  * n_problems = B > 1 makes one engine hold B independent MarginalDiBS + BGe problems (score-function estimator, one rank).  They share
- * every size (d, k, n_particles = M PER PROBLEM, S, Sa), the graph prior and every hyper-parameter; each has its own data, intervention mask,
- * PRNG key and M particles.  Device arrays hold B * M rows, problem-major: dibs_engine_get_state / set_state / read_buffer see all of them
+ * every size (d, k, n_particles = M PER PROBLEM, S, Sa), the graph prior and -- unless dibs_engine_set_problem_hparams says otherwise -- every
+ * hyper-parameter; each has its own data, intervention mask, PRNG key and M particles.  Device arrays hold B * M rows, problem-major: dibs_engine_get_state / set_state / read_buffer see all of them
  * (their key argument must be NULL), and each launch of a step covers the whole batch.  Problem p ends bit-identical to a standalone engine
  * run with (x_p, mask_p, key_p) and the same chunking.  dibs_engine_create rejects joint models, the reparam estimator, n_ranks != 1 and
  * n_particles >= 256; dibs_engine_set_data / init_particles / eval_gradients / step_* / the sharded loop and dibs_score_graphs are refused.
@@ -231,6 +232,30 @@ int dibs_engine_set_data_problem(dibs_engine* e, int32_t p, const float* x, int3
 int dibs_engine_init_particles_batch(dibs_engine* e, const uint32_t* keys);
 int dibs_engine_get_keys(dibs_engine* e, uint32_t* keys);
 int dibs_engine_set_keys(dibs_engine* e, const uint32_t* keys);
+
+/* PER-PROBLEM HYPER-PARAMETERS of a batched engine (a hyper-parameter sweep in one engine; the Python side is
+ * dibs_amd.inference.sample_sweep).  The seven double fields of dibs_config that select no size, code path or buffer -- each is a scalar a
+ * kernel of the standalone engine takes as a launch argument -- may differ between the problems of a batch.  A problem whose values were
+ * never set has the configuration's.  Everything else stays shared: sizes, prior / optimizer / estimator kind, rng_layout, tau,
+ * scale_latent, the BGe parameters.  Problem p still ends bit-identical to a standalone engine configured with p's values.
+ *   dibs_engine_set_problem_hparams(e, p, hp)   validated as dibs_engine_create validates the shared value (Erdos-Renyi: edge probability
+ *       in (0, 1); latent_prior_std <= 0: the default 1/sqrt(k)).  Only on a batched engine, and only before
+ *       dibs_engine_init_particles_batch / dibs_engine_set_state / the first dibs_engine_run (latent_prior_std enters the initial draw; the
+ *       device table is written once, then).  Values that differ from the configuration's need n_vars <= 64 and n_dim <= 64 (and the
+ *       default acyclicity pipe: not DIBS_ACYC_BF16): the kernels of the larger sizes take them as launch arguments of the whole batch.
+ *   dibs_engine_get_problem_hparams(e, p, hp)   the values in force (latent_prior_std as given, <= 0 meaning the default)
+ * Every misuse fails with a message that starts "batched engine: ". */
+typedef struct dibs_problem_hparams {
+  double alpha_linear;
+  double beta_linear;
+  double h_latent;
+  double stepsize;
+  double score_function_baseline;
+  double latent_prior_std;
+  double graph_prior_edges_per_node;
+} dibs_problem_hparams;
+int dibs_engine_set_problem_hparams(dibs_engine* e, int32_t p, const dibs_problem_hparams* hp);
+int dibs_engine_get_problem_hparams(dibs_engine* e, int32_t p, dibs_problem_hparams* hp);
 
 /* FLOAT64 ENGINE (no reference counterpart as such: the reference reaches double precision through JAX_ENABLE_X64,
  * dibs/models/nonlinearGaussian.py:183-185): dibs_config.reserved_i[1] = 64 makes the engine compute what the f64 build of the oracle
