@@ -60,7 +60,11 @@ __host__ __device__ inline int bge_tier(int n) { return n <= 32 ? (n + 3) / 4 - 
 // log(x) of a positive float with ~1e-7 ABSOLUTE error: x = 2^e m, m in [sqrt(1/2), sqrt(2)), log m = 2 atanh((m-1)/(m+1)).
 // (The Schur complement enters the score with a factor ~ (N + l) / 2: the relative error of logf on a value like log(400)
 //  would be amplified to 1e-5 .. 1e-4; a double-precision log costs ~100 instructions per problem.)
+// (No contraction in bge_log / bge_score / bge_score_pre: the instantiations of k_bge_chol reach the score through different functions
+//  -- table entries in registers or not -- and hipcc fused their multiply-adds differently: node scores of the batched engine one
+//  unit in the last place of a double from the standalone engine's at 65 .. 128 variables, found by tests/test_gpu_bge_tiers.py.)
 __device__ __forceinline__ double bge_log(float x) {
+#pragma clang fp contract(off)
   int e;
   float m = frexpf(x, &e);  // m in [0.5, 1)
   if (m < 0.70710678f) {
@@ -74,6 +78,7 @@ __device__ __forceinline__ double bge_log(float x) {
 
 // node score from the factorisation: ld2 = sum of log2 of the leading pivots, last = last pivot (see the file header)
 __device__ __forceinline__ double bge_score(const BgeParams& bp, int j, int l, int d, bool comp, float ld2, float last) {
+#pragma clang fp contract(off)
   const double Nn = bp.Nj[j];
   if (!(Nn > 0.0)) return 0.0;  // linearGaussian.py:118
   const double c = Nn + bp.alpha_lambd - d + l;
@@ -83,6 +88,7 @@ __device__ __forceinline__ double bge_score(const BgeParams& bp, int j, int l, i
 
 // the same with the table entries already in registers (k_bge_chol requests them before the factorisation)
 __device__ __forceinline__ double bge_score_pre(double Nn, double g, double ldRv, double alpha_lambd, int l, int d, bool comp, float ld2, float last) {
+#pragma clang fp contract(off)
   if (!(Nn > 0.0)) return 0.0;  // linearGaussian.py:118
   const double c = Nn + alpha_lambd - d + l;
   const double ld = 0.6931471805599453 * (double)ld2, ll = bge_log(last);

@@ -67,7 +67,7 @@ def test_init_particles_matches_oracle(c_oracle64):
     (20, 4, 64, 16, "uniform", (1,), "legacy"),
     (50, 4, 128, 32, "er", (0, 2), "legacy"),
     (70, 2, 32, 8, "er", (1,), "legacy"),           # > 64 variables: two mask words, 80x80 MFMA tiles
-    (112, 2, 16, 4, "er", (1,), "legacy"),          # engine maximum: 112x112 tiles, every BGe tier up to the one-problem-per-wave one
+    (112, 2, 16, 4, "er", (1,), "legacy"),          # engine maximum: 112x112 tiles; l = 35 .. 75 here, the one-problem-per-wave BGe tier ONLY (the other tiers at 65 .. 112 variables: test_gpu_bge_tiers.py)
     (96, 8, 64, 8, "er", (1,), "legacy"),           # thousands of queued problems at d > 80: only two waves of a factorisation block fit the
     (112, 6, 64, 4, "sf", (2,), "partitionable"),   # one-problem-per-wave tier, all four need quad index lists (LDS layout bug found by gpu_fuzz.py)
     (120, 2, 16, 4, "er", (1,), "legacy"),          # > 112: matrix powers through global memory, chunked edge scores, W through global memory
@@ -142,7 +142,7 @@ def test_marginal_bge_with_interventions(c_oracle64):
     (6, 2, 4, 2, 6, "one_observation"),  # a single observation
     (33, 2, 6, 2, 33, "d33"),            # one variable past two MFMA tiles; 64-bit masks half used
     (64, 1, 4, 2, 8, "d64"),             # mask word exactly full, n <= 32 via the complement form for every parent set
-    (65, 1, 4, 2, 8, "d65"),             # first size with two mask words and the one-problem-per-wave tier reachable
+    (65, 1, 4, 2, 8, "d65"),             # first size with two mask words; its one-problem-per-wave tier holds l = 32 alone, which these 260 parent sets need not contain (test_gpu_bge_tiers.py constructs it)
 ])
 def test_marginal_bge_edge_cases(c_oracle64, d, M, S, Sa, k, case):
     """Edge cases of the marginal step against the oracle: degenerate sizes, latent dimension != n_vars, a node without

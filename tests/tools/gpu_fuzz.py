@@ -198,6 +198,13 @@ def main():
                     note += f" graphs-differ({nflip} of {gg.size})"
                 elif nflip:
                     e, note = min(e, 0.0), note + f" ({nflip} Bernoulli boundary flips of {gg.size}: Z not compared)"
+                # node scores of the samples whose graph is the oracle's, entry by entry, to the bound of test_marginal_bge_step_stages
+                # (relative to the largest score: fp32 Cholesky pivots, the log-det error multiplied by (N + alpha_lambd - d + l) / 2)
+                ns_d = eng.read("NODE_SCORES").reshape(M, d, S).transpose(0, 2, 1)[same_s]   # device layout [m][j][s]
+                ns_o = np.asarray(dbg["node_scores"], np.float64)[same_s]
+                if ns_o.size and np.isfinite(ns_o).all():
+                    stage["NODE_SCORES"] = (float(np.abs(ns_d - ns_o).max() / max(np.abs(ns_o).max(), 1e-300)),
+                                            1e-4 if d <= 50 else (5e-4 if d <= 112 else 1e-3))
             lp_d, lp_o = eng.read("LOGPROBS_Z").reshape(M, S), np.asarray(dbg["logprobs_z"], np.float64).reshape(M, S)
             sel = np.ones((M, S), bool) if same_s is None else same_s
             if fam != "bge" and kw.get("grad_estimator_z") == "score" and np.isfinite(lp_o).all():
