@@ -317,9 +317,9 @@ extern "C" int dibs_score_graphs(dibs_engine* e, const int32_t* g, const float* 
     if (nn) {
       const NNParams np_ = nn_params(c);
       if (joint_nn_score_given(jg.jw, d_th.p, d_g.p, d_out.p, n, d, n_ho, np_, P, e->stream)) return fail("DenseNonlinearGaussian: scratch area: hipMalloc failed");
-    } else {
-      joint_lin_score_given(jg.jw, d_th.p, d_g.p, d_out.p, n, d, n_ho, (float)c.lin_obs_noise, (float)c.lin_mean_edge,
-                            (float)c.lin_sig_edge, e->stream);
+    } else if (joint_lin_score_given(jg.jw, d_th.p, d_g.p, d_out.p, n, d, n_ho, (float)c.lin_obs_noise, (float)c.lin_mean_edge,
+                                     (float)c.lin_sig_edge, e->stream)) {
+      return fail("LinearGaussian: scratch area: hipMalloc failed");
     }
     HIP_OK(hipStreamSynchronize(e->stream));
   } else {

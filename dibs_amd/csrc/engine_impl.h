@@ -20,9 +20,6 @@
 #include <mutex>
 #include <rccl/rccl.h>  // declarations only: librccl is bound at run time (dibs_rccl, engine_comm.hip), libdibs_hip.so does not link it
 #include "kernels_tail.h"
-#include "kernels_joint.h"
-#include "kernels_nn.h"
-#include "kernels_bge_soft.h"
 #include "exchange_ipc.h"
 
 #define LDS_LIMIT ((size_t)160 * 1024)
@@ -217,9 +214,6 @@ inline int need_batch(const dibs_engine* e) {
   if (e->B <= 1) return fail("not a batched engine (dibs_config.reserved_i[0] = n_problems must be > 1)");
   return 0;
 }
-
-template <typename K>
-inline void allow_lds(K kernel, size_t bytes) { dibs_allow_lds((const void*)kernel, bytes); }
 
 // Erdos-Renyi graph prior: the edge probability of the configuration, and its log odds (0 for the other priors)
 inline double er_edge_prob(const dibs_config& c) { return c.graph_prior_edges_per_node * c.n_vars / ((c.n_vars * (c.n_vars - 1)) / 2.0); }

@@ -201,7 +201,7 @@ static void launch_kmat(dibs_engine* e, hipStream_t st, const KmatRows& z, const
                        (float)c.scale_theta, (float)c.h_theta, ksym, (const float*)e->kz, e->ksum);
 }
 
-// the launch arguments of the joint models' estimators (kernels_joint.h); LinearGaussian sets its three prior floats afterwards
+// the launch arguments of the joint models' estimators (joint_launch.h); LinearGaussian sets its three prior floats afterwards
 static JointLaunch joint_launch_args(dibs_engine* e, const RowTarget& rt, int Mg, float alpha) {
   const dibs_config& c = e->cfg;
   return JointLaunch{e->stream, e->z, e->theta, e->scores, e->thr, e->w_lik, e->logprobs_z, e->logprobs_th, e->baseline,
@@ -468,11 +468,11 @@ int step_local(dibs_engine* e, int t, const RowTarget& rt, const StepKeys* xk, i
     jl.sig_edge = (float)c.lin_sig_edge;
     {
       KTimer tm(e, DIBS_K_LIN_THETA);  // ("lin_logprobs": both log-prob launches)
-      joint_lin_all_logprobs(&e->jw, jl, carry_theta, carry_lik);
+      if (joint_lin_all_logprobs(&e->jw, jl, carry_theta, carry_lik)) return fail("LinearGaussian: scratch area: hipMalloc failed");
     }
     {
       KTimer tm(e, DIBS_K_LIN_Z);      // ("lin_grad": the theta and the Z estimator in one launch)
-      joint_lin_all_grads(&e->jw, jl, carry_theta, carry_lik);
+      if (joint_lin_all_grads(&e->jw, jl, carry_theta, carry_lik)) return fail("LinearGaussian: scratch area: hipMalloc failed");
       if (!xk) std::swap(e->baseline, e->baseline2);  // (explicit-key evaluation: the loop's baselines stay, the updated ones are read from baseline2)
     }
   } else if (c.likelihood == DIBS_LIK_DENSENN) {

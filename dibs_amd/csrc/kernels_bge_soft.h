@@ -20,17 +20,10 @@
 // One wave per node (lane = matrix row; two rows per lane for d > 64), one block per (particle, sample).  L (column-major) and the
 // columns of L^-1 are packed triangles in LDS: 2 * d (d + 1) / 2 floats per wave.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#ifndef DIBS_TU_BGE_SOFT
+#error "kernels_bge_soft.h defines kernels that are not templates: it is compiled in tu_bge_soft.hip only"
+#endif
 #include "kernels_joint.h"
-#include <stdlib.h>
-
-struct BgeSoftParams {
-  const float* R;     // [n_mats, d, d]
-  const double* Nj;   // [d]
-  double alpha_lambd, alpha_mu, log_t;
-  int n_mats;
-};
 
 __device__ __forceinline__ double digamma_d(double x) {
   double acc = 0.0;
@@ -44,20 +37,6 @@ __device__ __forceinline__ double digamma_d(double x) {
   return acc + log(x) - 0.5 / x - ser;
 }
 
-__host__ __device__ inline int bge_soft_tri(int d) { return d * (d + 1) / 2; }
-__host__ __device__ inline size_t bge_soft_wave_bytes(int d) {
-  // L tri | U tri | p[128] | y[128] | w[128] | dinv[128]
-  return (((size_t)2 * bge_soft_tri(d) + 4 * 128) * 4 + 15) & ~(size_t)15;
-}
-__host__ __device__ inline size_t bge_soft_shared_bytes(int d, bool r_in_lds) {
-  return ((((size_t)d * d * (r_in_lds ? 1 : 0)) * 4 + 15) & ~(size_t)15) + 256;  // Rs | red[4] (+ pad)
-}
-__host__ __device__ inline int bge_soft_waves(int d, bool r_in_lds) {
-  const size_t shared = bge_soft_shared_bytes(d, r_in_lds);
-  if (shared + bge_soft_wave_bytes(d) > (size_t)160 * 1024 - 1024) return 0;
-  const int nw = (int)(((size_t)160 * 1024 - 1024 - shared) / bge_soft_wave_bytes(d));
-  return nw > 4 ? 4 : nw;
-}
 __host__ __device__ inline size_t bge_soft_lds_bytes(int d, bool r_in_lds) {
   return bge_soft_shared_bytes(d, r_in_lds) + (size_t)bge_soft_waves(d, r_in_lds) * bge_soft_wave_bytes(d);
 }
@@ -269,8 +248,6 @@ __global__ __launch_bounds__(256) void k_bge_soft(const float* __restrict__ scor
   }
 }
 
-#ifdef DIBS_TU_BGE_SOFT
-#include "kernels_bge_soft_mf.h"
 // softmax over the samples and W = sum_s w_s dS_s (samples with w_s == 0 in float are skipped, in sample order)
 // grid = (Mloc, ceil(d*d / 256)), block = 256: every block of a particle evaluates the S weights itself (128 exponentials) and sums one
 // 256-element slice of the S x d x d gradients -- with one block per particle half of the CUs stood idle behind 164 MB of reads (126 us).
@@ -307,51 +284,3 @@ __global__ __launch_bounds__(256) void k_soft_combine(const float* __restrict__ 
     w_lik[(size_t)m * dd + e] = acc;
   }
 }
-
-// both launches of the estimator: per-sample soft-graph scores + gradients, then the softmax-weighted combination
-void bge_soft_launch(const BgeSoftParams& sp, const float* scores, Key2 carry, int m0, int M, int Mloc, int d, int S, float alpha,
-                     float tau, int layout, int tiny, float* soft_ds, float* logprobs, float* w_lik, hipStream_t stream, float* tri_glob,
-                     int glob_blocks) {
-  if (d > 128) {  // packed triangles in global scratch (tri_glob: glob_blocks * 4 waves * 2 * tri(d) floats), persistent blocks
-    hipLaunchKernelGGL((k_bge_soft<false, 4, true>), dim3(glob_blocks), dim3(256), bge_soft_glob_lds_bytes(), stream, scores, sp, carry, m0, M, d, S,
-                       alpha, tau, layout, tiny, soft_ds, logprobs, tri_glob, S * Mloc);
-    hipLaunchKernelGGL(k_soft_combine, dim3(Mloc, (d * d + 255) / 256), dim3(256), (size_t)S * 4 + 16, stream, soft_ds, logprobs, w_lik, d, S);
-    return;
-  }
-  const bool rl = sp.n_mats == 1 && bge_soft_waves(d, true) >= (bge_soft_waves(d, false) < 4 ? bge_soft_waves(d, false) : 4);
-  const size_t lds = bge_soft_lds_bytes(d, rl);
-#define SOFT_LAUNCH(RL_, RPL_)                                                                                                          \
-  {                                                                                                                                     \
-    if (lds > 48 * 1024) hipFuncSetAttribute((const void*)k_bge_soft<RL_, RPL_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL((k_bge_soft<RL_, RPL_>), dim3(S, Mloc), dim3(256), lds, stream, scores, sp, carry, m0, M, d, S, alpha, tau, layout, \
-                       tiny, soft_ds, logprobs, (float*)nullptr, 1);                                                                    \
-  }
-  if (d <= 64) {
-    // blocked factorisation on the matrix pipe (kernels_bge_soft_mf.h)
-    const bool rr = sp.n_mats == 1;
-    const size_t l2 = bsm_lds_bytes(d, rr);
-#define SOFTM(NB_, RL_, W_)                                                                                                             \
-  {                                                                                                                                     \
-    if (l2 > 48 * 1024) hipFuncSetAttribute((const void*)k_bge_soft_mf<NB_, RL_, W_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2); \
-    hipLaunchKernelGGL((k_bge_soft_mf<NB_, RL_, W_>), dim3(S, Mloc), dim3(256), l2, stream, scores, sp, carry, m0, M, d, S, alpha, tau, layout, \
-                       tiny, soft_ds, logprobs);                                                                                        \
-  }
-    // (three waves per SIMD: 165 registers, no scratch -- 4.6 ms against 5.4 at two)
-    switch ((d + 15) / 16) {
-      case 1: if (rr) SOFTM(1, true, 3) else SOFTM(1, false, 3) break;
-      case 2: if (rr) SOFTM(2, true, 3) else SOFTM(2, false, 3) break;
-      case 3: if (rr) SOFTM(3, true, 3) else SOFTM(3, false, 3) break;
-      default: if (rr) SOFTM(4, true, 3) else SOFTM(4, false, 3) break;
-    }
-#undef SOFTM
-  } else {
-    if (rl) SOFT_LAUNCH(true, 2) else SOFT_LAUNCH(false, 2)
-  }
-#undef SOFT_LAUNCH
-  hipLaunchKernelGGL(k_soft_combine, dim3(Mloc, (d * d + 255) / 256), dim3(256), (size_t)S * 4 + 16, stream, soft_ds, logprobs, w_lik, d, S);
-}
-#else
-void bge_soft_launch(const BgeSoftParams& sp, const float* scores, Key2 carry, int m0, int M, int Mloc, int d, int S, float alpha,
-                     float tau, int layout, int tiny, float* soft_ds, float* logprobs, float* w_lik, hipStream_t stream, float* tri_glob,
-                     int glob_blocks);
-#endif  // DIBS_TU_BGE_SOFT

@@ -17,6 +17,9 @@
 //   * the matrix is kept as A - I (diagonal entries p^2 (R_vv - 1)): pivots minus one stay exact for small p, as in k_bge_soft_reg.
 // LDS per wave 3.3 KB (k_bge_soft_reg: 13.4 KB): occupancy is set by registers.  Block algebra checked in tests/tools/bge_soft_blocked_emulation.py.
 #pragma once
+#ifndef DIBS_TU_BGE_SOFT
+#error "kernels_bge_soft_mf.h is compiled in tu_bge_soft.hip only"
+#endif
 #include "kernels_bge_soft.h"
 
 #define BSM_LDP 20  // row stride (floats) of the 16 x 16 LDS blocks: 16-byte rows, lanes of a 16-lane group on distinct banks

@@ -1,13 +1,16 @@
 // JointDiBS + LinearGaussian, GRAM-MATRIX path: any number of observations.   reference: dibs/models/linearGaussian.py:278-338
-// The tuned kernels of kernels_joint.h keep x [N, d] in LDS and form x (g o theta) per sample on MFMA; they stop where x no longer
+// The tuned kernels of kernels_lin.h keep x [N, d] in LDS and form x (g o theta) per sample on MFMA; they stop where x no longer
 // fits (about 290 observations at d = 50).  The likelihood only needs second moments of x:
 //   sum_{n not intervened on j} (x_nj - (x w_j)_n)^2 = C_jj - 2 w_j^T C_:j + w_j^T C w_j,     C = C^(j) = sum_n x_n x_n^T over those n,
 //   x^T r_j = (C_:j - C w_j) / obs_noise                                                    (w_j = g[:, j] o theta[:, j])
 // so one d x d (interventions: d of them) double-precision Gram matrix, built once per data set on the host, replaces x.  The
 // quadratic form cancels (terms ~ N var(x), result ~ N obs_noise): it is evaluated in double on the vector ALU.  Cost per sample:
 // d^3 FMA for soft graphs, sum_j l_j d for hard ones -- independent of N.
-// (included by kernels_joint.h inside its translation unit)
 #pragma once
+#ifndef DIBS_TU_LIN
+#error "kernels_lin_gram.h defines kernels that are not templates: it is compiled in tu_lin.hip only"
+#endif
+#include "kernels_lin.h"  // (LinGradJob)
 
 // v[a][j] = sum_b C^(j)[a][b] w[b][j] for the pairs this thread owns; calls f(a, j, v, c_aj)
 template <typename F>

@@ -1,8 +1,10 @@
 // JointDiBS + DenseNonlinearGaussian: log p(theta, D | G_s) of all samples with the first layer on the f16 matrix pipe (gfx950)
 #pragma once
+#ifndef DIBS_TU_NN
+#error "kernels_nn_f16.h defines kernels that are not templates: it is compiled in tu_nn.hip only"
+#endif
 #include "kernels_nn.h"
 #include "kernels_acyc_f16.h"
-#include <type_traits>
 
 // ------------------------------------------------------------------------------------------------
 // K-NN-hf  k_nn_logprobs (kernels_nn.h; reference: nonlinearGaussian.py:35-81, 248-326) with the per-hidden-unit product
@@ -38,7 +40,6 @@ __host__ __device__ inline size_t nhf_lds_bytes(int d, int NT, int H, bool soft)
   return img + graphs + lvt + 64 * 8 + 64;
 }
 
-#ifdef DIBS_TU_NN
 // ew[m]: exponent that brings max |W1[m]| into [2^13, 2^14) (the f16 pieces of g o W1 then stay below 2^14).  grid = Mloc, block = 1024
 // (eight loads in flight per thread: a rolled loop with one load per trip took 97 us for the 51 MB of config 5)
 __global__ __launch_bounds__(1024) void k_nn_w1_exp(const float* __restrict__ theta, size_t P, int* __restrict__ ew, int d, int H) {
@@ -82,7 +83,6 @@ __global__ __launch_bounds__(256) void k_nn_tables_hf(const float* __restrict__ 
   ahf_split(v0, v1, 1.0f, ph, pm);
   w1p[o] = make_uint2(ph, pm);
 }
-#endif
 
 template <int NT>
 struct NhfFrag {

@@ -1,5 +1,8 @@
 // JointDiBS + DenseNonlinearGaussian log-probs on the f16 matrix pipe, per-sample operand in REGISTERS (gfx950)
 #pragma once
+#ifndef DIBS_TU_NN
+#error "kernels_nn_f16x.h defines kernels that are not templates: it is compiled in tu_nn.hip only"
+#endif
 #include "kernels_nn_f16.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -34,7 +37,6 @@ __host__ __device__ inline size_t nhx_lds_bytes(int d, int NT, int N, int H, boo
   return nhx_img_bytes(NT, N) + nhx_graph_bytes(d, soft) + ((size_t)2 * H + 1) * nhf_dp4(d) * 4 + 64 * 8 + 64;
 }
 
-#ifdef DIBS_TU_NN
 // w1q_s[m][h][aq][j] = W1[j][4 aq .. 4 aq + 3][h] 2^ew  (float4; inputs beyond d: 0)
 // w1q_p[m][h][aq][j] = their packed f16 pieces {h(a0,a1), h(a2,a3), m(a0,a1), m(a2,a3)}
 // A block takes 16 nodes x 16 inputs (4 quads) of one particle with ALL hidden units through LDS: theta's layout W1[j][a][h] is read in runs of
@@ -66,7 +68,6 @@ __global__ __launch_bounds__(256) void k_nn_tables_hx(const float* __restrict__ 
     w1q_p[q] = make_uint4(h0, h1, m0, m1);
   }
 }
-#endif
 
 template <int NT, int NTN, int ACT, bool SOFT>
 __global__ __launch_bounds__(64 * NT) void k_nn_logprobs_hx(const float* __restrict__ x, const int32_t* __restrict__ mask, const float* __restrict__ theta,

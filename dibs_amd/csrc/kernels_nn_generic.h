@@ -7,7 +7,10 @@
 // thread that sums over the observations in order (results are run-to-run reproducible).
 // theta row layout (pytree leaf order of the reference): for every Dense layer l: W_l [d][in_l][out_l] | b_l [d][out_l] (with bias).
 #pragma once
-// (included by kernels_nn.h inside its translation unit, after NNParams / nn_act / the lin_* helpers)
+#ifndef DIBS_TU_NN
+#error "kernels_nn_generic.h defines kernels that are not templates: it is compiled in tu_nn.hip only"
+#endif
+#include "kernels_nn.h"  // (nn_act, the lin_* helpers)
 
 struct NNNet {
   int nl;                                   // Dense layers = hidden layers + 1

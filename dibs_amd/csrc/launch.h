@@ -1,5 +1,6 @@
-// Host-side launchers of the kernel families that live in their own translation units (tu_*.hip): plain arguments, no templates,
-// so the engine's files (engine*.hip) do not instantiate those kernels.
+// Host-side launchers of the kernel families that live in their own translation units (tu_*.hip): plain arguments, no templates over a
+// kernel, so the engine's files (engine*.hip) neither see nor instantiate those kernels.  The joint models and the soft-graph BGe
+// estimator: joint_launch.h (included below).
 #pragma once
 #include "common.h"
 #include "kernels_kmat.h"
@@ -9,6 +10,9 @@
 // kernels that may need more than the default 64 KiB of dynamic LDS: raises hipFuncAttributeMaxDynamicSharedMemorySize once per
 // (device, kernel) and size increase (engine.hip; thread-safe -- engines on several devices / host threads share the table)
 void dibs_allow_lds(const void* kernel, size_t bytes);
+template <typename K>
+inline void allow_lds(K kernel, size_t bytes) { dibs_allow_lds((const void*)kernel, bytes); }
+int dibs_cu_count();  // (engine.hip: compute units of the current device)
 
 // ---- tu_bge.hip --------------------------------------------------------------------------------------
 // sampling + queueing (sample = false: parent sets given in `masks`); kf.z != null appends the kernel-matrix blocks
@@ -70,3 +74,5 @@ void f64_launch_grad(hipStream_t st, const F64Args& a);
 void f64_launch_kmat(hipStream_t st, const F64Args& a);
 void f64_launch_phi(hipStream_t st, const F64Args& a);
 void f64_launch_update(hipStream_t st, const F64Args& a);
+
+#include "joint_launch.h"

@@ -3,9 +3,6 @@
 #include "launch.h"
 #include <stdlib.h>
 
-template <typename K>
-static void allow_lds(K kernel, size_t bytes) { dibs_allow_lds((const void*)kernel, bytes); }
-
 size_t bge_sample_lds_bytes(int d, int S, int W) { return 4 * bge_sample_wave_bytes(d, S, W); }
 
 void bge_launch_sample(bool sample, hipStream_t stream, const uint32_t* thr, uint64_t* masks, double* node_scores, const BgeParams& bp,

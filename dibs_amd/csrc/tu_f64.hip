@@ -2,9 +2,6 @@
 #include "launch.h"
 #include "kernels_f64.h"
 
-template <typename K>
-static void allow_lds(K kernel, size_t bytes) { dibs_allow_lds((const void*)kernel, bytes); }
-
 void f64_launch_edge(hipStream_t st, const F64Args& a) { hipLaunchKernelGGL(k64_edge, dim3(a.M), dim3(256), 0, st, a); }
 
 void f64_launch_bge(hipStream_t st, const F64Args& a) {
