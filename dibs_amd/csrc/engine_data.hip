@@ -64,26 +64,39 @@ static int bge_host_stats(BgeHost* st, const dibs_config& cfg, int d, int N, con
   R.assign((size_t)n_mats * d * d, 0.0);
   Nj.assign(d, 0.0);
   gam.assign((size_t)d * (d + 1), 0.0);
-  std::vector<double> xb(d);
+  // With interventions this is d matrices of d^2 sums over N rows (1.3e10 products at d = 256, N = 768: 18 s as a plain triple loop, found
+  // by tests/test_gpu_max_size.py).  The sums s[a][b] = s[b][a] run over the centred rows xc of the node, b innermost: every s[a][b] adds
+  // the same terms in the same order as the triple loop did (a row that is left out adds 0 * 0), so R is the same to the last bit.
+  std::vector<double> xb(d), xc((size_t)N * d), s(d);
   for (int jm = 0; jm < n_mats; ++jm) {
     double Nn = 0;
     for (int n = 0; n < N; ++n) Nn += (any && mask[(int64_t)n * d + jm]) ? 0.0 : 1.0;
     for (int a = 0; a < d; ++a) {
-      double s = 0;
+      double sa = 0;
       for (int n = 0; n < N; ++n)
-        if (!(any && mask[(int64_t)n * d + jm])) s += (double)x[(int64_t)n * d + a];
-      xb[a] = Nn > 0 ? s / Nn : 0.0;
+        if (!(any && mask[(int64_t)n * d + jm])) sa += (double)x[(int64_t)n * d + a];
+      xb[a] = Nn > 0 ? sa / Nn : 0.0;
     }
-    for (int a = 0; a < d; ++a)
-      for (int b = 0; b < d; ++b) {
-        double s = 0;
-        for (int n = 0; n < N; ++n)
-          if (!(any && mask[(int64_t)n * d + jm]))
-            s += ((double)x[(int64_t)n * d + a] - xb[a]) * ((double)x[(int64_t)n * d + b] - xb[b]);
-        const double ma = mean_obs ? (double)mean_obs[a] : 0.0, mb = mean_obs ? (double)mean_obs[b] : 0.0;
-        const double v = (a == b ? small_t : 0.0) + s + (Nn * amu / (Nn + amu)) * (xb[a] - ma) * (xb[b] - mb);
-        R[(size_t)jm * d * d + (size_t)a * d + b] = v;
+    for (int n = 0; n < N; ++n) {
+      const bool out = any && mask[(int64_t)n * d + jm];
+      for (int a = 0; a < d; ++a) xc[(size_t)n * d + a] = out ? 0.0 : (double)x[(int64_t)n * d + a] - xb[a];
+    }
+    const double f = Nn * amu / (Nn + amu);
+    for (int a = 0; a < d; ++a) {
+      for (int b = a; b < d; ++b) s[b] = 0;
+      for (int n = 0; n < N; ++n) {
+        const double* __restrict__ row = xc.data() + (size_t)n * d;
+        double* __restrict__ sp = s.data();
+        const double xa = row[a];
+        for (int b = a; b < d; ++b) sp[b] += xa * row[b];
       }
+      const double ma = mean_obs ? (double)mean_obs[a] : 0.0;
+      for (int b = a; b < d; ++b) {
+        const double mb = mean_obs ? (double)mean_obs[b] : 0.0;
+        R[(size_t)jm * d * d + (size_t)a * d + b] = (a == b ? small_t : 0.0) + s[b] + f * (xb[a] - ma) * (xb[b] - mb);
+        if (b != a) R[(size_t)jm * d * d + (size_t)b * d + a] = 0.0 + s[b] + f * (xb[b] - mb) * (xb[a] - ma);
+      }
+    }
     if (any) Nj[jm] = Nn;
     else
       for (int j = 0; j < d; ++j) Nj[j] = Nn;

@@ -9,7 +9,8 @@
 //     reference: graph_utils.py:8-28, dibs.py:121-140, 557-601
 // grid = (ceil(Sa / CPB), Mloc), block = 256; dynamic LDS = 3 * DP * LD * 4, DP = 16 NT, LD = DP + 2
 //
-// Serves d <= 32 and 65 <= d <= 112 (and unpaired PRNG layouts); 33 <= d <= 64 runs on kernels_acyc_bf16.h.  At the headline size
+// Serves d <= 32, and up to d = 112 the chains that cannot be paired (odd Sa) and DIBS_ACYC_F32=1 runs; 33 <= d <= 112 with paired chains
+// runs on kernels_acyc_f16.h by default (tu_acyc.hip; DIBS_ACYC_BF16=1: kernels_acyc_bf16.h).  At the headline size
 // (d = 50, measured while this was the production kernel): 5.96 M MFMAs = 186 k MFMA cycles per SIMD + 20.1 M other vector
 // instructions = 78 k cycles of the ~350 k the launch takes (141.5 us, 32 % of the FP32 peak; f32 MFMAs do not overlap with the
 // vector work of co-resident waves).  Measured on the box and reverted:

@@ -271,28 +271,48 @@ static void bge_prepare(const dibs_config* c, const real* x, const int32_t* mask
   b->R = (real*)malloc(sizeof(real) * (size_t)b->n_mats * d * d);
   b->Nj = (double*)malloc(sizeof(double) * d);
   b->gam = (double*)malloc(sizeof(double) * d * (d + 1));
-  double* xb = (double*)malloc(sizeof(double) * d);
-  double* Rm = (double*)malloc(sizeof(double) * d * d);
-  for (int jm = 0; jm < (any ? d : 1); ++jm) {
-    double Nn = 0;
-    for (int n = 0; n < N; ++n) Nn += (any && mask[(int64_t)n * d + jm]) ? 0.0 : 1.0;
-    for (int a = 0; a < d; ++a) {
-      double s = 0;
-      for (int n = 0; n < N; ++n)
-        if (!(any && mask[(int64_t)n * d + jm])) s += (double)x[(int64_t)n * d + a];
-      xb[a] = Nn > 0 ? s / Nn : 0.0;
-    }
-    for (int a = 0; a < d; ++a)
-      for (int bb = 0; bb < d; ++bb) {
+  /* One matrix per node with interventions: d^3 N products (1.3e10 at d = 256, N = 768), so the nodes are shared between threads and
+   * each sum runs over the centred columns xc[a][.] of the node's own rows.  The value of every sum is the one of the plain triple loop:
+   * same terms in the same order (a row that is left out adds 0 * 0), s[a][bb] = s[bb][a] term by term. */
+#pragma omp parallel
+  {
+    double* xb = (double*)malloc(sizeof(double) * d);
+    double* Rm = (double*)malloc(sizeof(double) * d * d);
+    double* xc = (double*)malloc(sizeof(double) * (size_t)d * N);
+#pragma omp for schedule(dynamic)
+    for (int jm = 0; jm < (any ? d : 1); ++jm) {
+      double Nn = 0;
+      for (int n = 0; n < N; ++n) Nn += (any && mask[(int64_t)n * d + jm]) ? 0.0 : 1.0;
+      for (int a = 0; a < d; ++a) {
         double s = 0;
         for (int n = 0; n < N; ++n)
-          if (!(any && mask[(int64_t)n * d + jm]))
-            s += ((double)x[(int64_t)n * d + a] - xb[a]) * ((double)x[(int64_t)n * d + bb] - xb[bb]);
-        double ma = mean_obs ? (double)mean_obs[a] : 0.0, mb = mean_obs ? (double)mean_obs[bb] : 0.0;
-        Rm[a * d + bb] = (a == bb ? b->small_t : 0.0) + s + (Nn * amu / (Nn + amu)) * (xb[a] - ma) * (xb[bb] - mb);
+          if (!(any && mask[(int64_t)n * d + jm])) s += (double)x[(int64_t)n * d + a];
+        xb[a] = Nn > 0 ? s / Nn : 0.0;
+        for (int n = 0; n < N; ++n)
+          xc[(size_t)a * N + n] = (any && mask[(int64_t)n * d + jm]) ? 0.0 : (double)x[(int64_t)n * d + a] - xb[a];
       }
-    for (int i = 0; i < d * d; ++i) b->R[(size_t)jm * d * d + i] = (real)Rm[i];
-    if (any) b->Nj[jm] = Nn; else for (int j = 0; j < d; ++j) b->Nj[j] = Nn;
+      for (int a = 0; a < d; ++a)
+        for (int bb = 0; bb < d; ++bb) {
+          double s = 0;
+          if (bb < a) {
+            s = Rm[bb * d + a];   /* (holds the plain sum until the row a = bb is finished below) */
+          } else {
+            const double *pa = xc + (size_t)a * N, *pb = xc + (size_t)bb * N;
+            for (int n = 0; n < N; ++n) s += pa[n] * pb[n];
+          }
+          Rm[a * d + bb] = s;
+        }
+      for (int a = 0; a < d; ++a)
+        for (int bb = 0; bb < d; ++bb) {
+          double ma = mean_obs ? (double)mean_obs[a] : 0.0, mb = mean_obs ? (double)mean_obs[bb] : 0.0;
+          Rm[a * d + bb] = (a == bb ? b->small_t : 0.0) + Rm[a * d + bb] + (Nn * amu / (Nn + amu)) * (xb[a] - ma) * (xb[bb] - mb);
+        }
+      for (int i = 0; i < d * d; ++i) b->R[(size_t)jm * d * d + i] = (real)Rm[i];
+      if (any) b->Nj[jm] = Nn; else for (int j = 0; j < d; ++j) b->Nj[j] = Nn;
+    }
+    free(xb);
+    free(Rm);
+    free(xc);
   }
   for (int j = 0; j < d; ++j)
     for (int l = 0; l <= d; ++l) {
@@ -301,8 +321,6 @@ static void bge_prepare(const dibs_config* c, const real* x, const int32_t* mask
                                 lgamma(0.5 * (al - d + l + 1)) - 0.5 * Nn * log(M_PI) +
                                 0.5 * (al - d + 2 * l + 1) * log(b->small_t);
     }
-  free(xb);
-  free(Rm);
 }
 static void bge_free(bge_pre* b) { free(b->R); free(b->Nj); free(b->gam); }
 

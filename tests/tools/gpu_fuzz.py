@@ -15,6 +15,8 @@ from dibs_amd._abi import make_config          # noqa: E402
 from dibs_amd.engine import Engine             # noqa: E402
 from oracle import prng                        # noqa: E402
 from oracle.c_oracle import COracle            # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from large_states import clustered_sparse_state   # noqa: E402
 
 
 def rel(a, b):
@@ -88,11 +90,11 @@ def draw(rng):
         kw["edges_per_node"] = 0.4 if d <= 3 else (1 if d <= 9 else 2)
         kw.pop("bge_alpha_lambd", None)
         kw["n_observations"] = N = int(rng.choice([20, 100]))
-    if os.environ.get("FUZZ_WIDE"):   # 113 .. 224 variables: the global-memory paths (marginal BGe, score estimator); three / four mask words
+    if os.environ.get("FUZZ_WIDE"):   # 113 .. 256 variables: the global-memory paths (marginal BGe, score estimator); three / four mask words
         fam = "bge"
         for k_ in ("joint", "likelihood", "lin_obs_noise", "lin_sig_edge", "lin_mean_edge", "nn_hidden", "nn_activation", "nn_bias", "nn_obs_noise"):
             kw.pop(k_, None)
-        kw["n_vars"] = d = int(rng.choice([113, 120, 127, 128, 129, 144, 160, 191, 192, 193, 224]))
+        kw["n_vars"] = d = int(rng.choice([113, 120, 127, 128, 129, 144, 160, 191, 192, 193, 224, 225, 241, 255, 256]))
         kw["n_dim"] = int(rng.choice([d, d, d // 2, 40]))
         kw["n_particles"] = int(rng.choice([1, 2, 3, 6]))
         kw["n_grad_mc_samples"] = int(rng.choice([2, 5, 8, 16]))
@@ -107,6 +109,8 @@ def draw(rng):
     interv = rng.random() < 0.3 and N > 1
     kw["has_interventions"] = bool(interv)
     t = int(rng.choice([0, 1, 2, 7, 30]))
+    if d > 210:   # (the sparse state of main() is sparse through alpha = alpha_linear t: the step index at which alpha = 20)
+        t = int(round(20.0 / kw["alpha_linear"]))
     return fam, kw, interv, t
 
 
@@ -139,6 +143,10 @@ def main():
         # noise of the sum get a coin flip (in the reference as well).  A trajectory starts at t = 0 with a clean prior gradient; a trial
         # that starts in the middle gets a unit second-moment estimate instead.
         st["v_z"] = np.ones_like(st["v_z"])
+        if d > 210:
+            # fresh particles have soft graphs around 1/2 and (I + G/d)^(d-1) ~ 1.5^d leaves float32 near d = 220: a trial would compare
+            # infinities.  Sparse, neighbouring particles instead (tests/large_states.py; its own seeded generator: `rng` is not touched)
+            st["z"] = clustered_sparse_state(st["z"], 0.6, 2.0, seed=trial)
         if st.get("v_theta") is not None:
             st["v_theta"] = np.ones_like(st["v_theta"])
         worst, note = 0.0, ""

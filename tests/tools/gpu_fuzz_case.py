@@ -6,7 +6,7 @@ from dibs_amd._abi import make_config
 from dibs_amd.engine import Engine
 from oracle import prng
 from oracle.c_oracle import COracle
-from gpu_fuzz import draw, rel
+from gpu_fuzz import clustered_sparse_state, draw, rel
 
 seed = int(sys.argv[1]); want = [int(a) for a in sys.argv[2:]]
 rng = np.random.default_rng(seed)
@@ -28,6 +28,7 @@ for trial in range(max(want) + 1):
     eng.set_data(x, mask)
     st = co.new_state(cfg, key)
     st["v_z"] = np.ones_like(st["v_z"])
+    if d > 210: st["z"] = clustered_sparse_state(st["z"], 0.6, 2.0, seed=trial)   # (as gpu_fuzz.py: sparse, neighbouring particles)
     if st.get("v_theta") is not None: st["v_theta"] = np.ones_like(st["v_theta"])
     print(f"== trial {trial} {fam} t={t}", {k: v for k, v in kw.items()})
     for step in (t, t + 1):
