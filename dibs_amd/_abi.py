@@ -90,10 +90,11 @@ def make_config(*, n_vars, n_particles, n_observations, n_dim=None, joint=False,
                 logistic_minval_tiny=False, has_interventions=False, bge_alpha_mu=1.0, bge_alpha_lambd=None,
                 lin_obs_noise=0.1, lin_mean_edge=0.0, lin_sig_edge=1.0, lin_min_edge=0.5,
                 nn_hidden=(5,), nn_activation="relu", nn_bias=True, nn_obs_noise=0.1, nn_sig_param=1.0,
-                rank=0, n_ranks=1, device_id=0, n_problems=1, precision=32):
+                rank=0, n_ranks=1, device_id=0, n_problems=1, precision=32, n_chains=0):
     """Build a dibs_config with the reference's defaults (svgd.py:60-83 marginal, :425-448 joint).  ``n_problems`` > 1: a batched
     engine of that many independent problems of ``n_particles`` particles each (include/dibs_hip.h, reserved_i[0]).  ``precision``
-    64: the float64 engine (reserved_i[1]; 32 = float32, the default)."""
+    64: the float64 engine (reserved_i[1]; 32 = float32, the default).  ``n_chains`` > 1: a chains engine of that many chains of one
+    joint model on one data set, ``n_particles`` particles each (reserved_i[2]; 0 or 1: the standalone engine)."""
     c = DibsConfig()
     c.abi_version = ABI_VERSION
     c.n_vars = int(n_vars)
@@ -123,6 +124,7 @@ def make_config(*, n_vars, n_particles, n_observations, n_dim=None, joint=False,
     c.rank, c.n_ranks, c.device_id = int(rank), int(n_ranks), int(device_id)
     c.reserved_i[0] = int(n_problems)
     c.reserved_i[1] = 0 if int(precision) == 32 else int(precision)   # (0: float32, the layout of every config before the field)
+    c.reserved_i[2] = int(n_chains)
     c.alpha_linear = float((0.05 if joint else 1.0) if alpha_linear is None else alpha_linear)
     c.beta_linear = float(beta_linear)
     c.tau = float(tau)

@@ -17,6 +17,7 @@ struct ProblemHP {
   float prior_c;            // log odds of the Erdos-Renyi edge probability (0 for the other priors)
   float inv_sig2;           // 1 / latent_prior_std^2
   float h, stepsize;        // kernel bandwidth, optimizer step size
+  float h_theta;            // chains engines (joint models): bandwidth of the parameter kernel (the segment theta of k_phi_update)
 };
 
 __device__ __forceinline__ float wave_sum(float v) {

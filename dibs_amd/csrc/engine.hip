@@ -32,7 +32,7 @@ static int64_t theta_size(const dibs_config& c) {
 // Batched engines: do the kernels of a step take the per-problem values from the device table?  The sizes whose kernels have table-reading
 // forms (k_edge_scores_p, k_acyc<NT> / k_acyc_hf, k_particle_grad with W, U, V in LDS); beyond them the launch arguments of the whole batch.
 static bool batch_hp_tier(const dibs_engine* e) {
-  return e->B > 1 && e->d <= 64 && e->k <= 64 && e->w_tot == nullptr && e->tune.acyc_pipe != DIBS_PIPE_BF16;
+  return e->B > 1 && !e->chains && e->d <= 64 && e->k <= 64 && e->w_tot == nullptr && e->tune.acyc_pipe != DIBS_PIPE_BF16;
 }
 
 // Engines alive in this process.  The in-kernel flags (fork: k_wait_flag, join: tail_join_wait) are used by an engine that is ALONE in its
@@ -48,6 +48,8 @@ static int engine_alloc(dibs_engine* e, const dibs_config& c, void* stream) {
   e->d = c.n_vars;
   e->k = c.n_dim;
   e->B = c.reserved_i[0] > 1 ? c.reserved_i[0] : 1;
+  e->chains = c.reserved_i[2] > 1;  // chains engine: the row layout of a batched engine of n_chains "problems" (dibs_engine_create: n_problems <= 1)
+  if (e->chains) e->B = c.reserved_i[2];
   e->M = c.n_particles;
   e->Mloc = e->B > 1 ? e->B * c.n_particles : c.n_particles / c.n_ranks;
   e->m0 = c.rank * (c.n_particles / c.n_ranks);
@@ -194,6 +196,7 @@ static int engine_alloc(dibs_engine* e, const dibs_config& c, void* stream) {
     HIP_OK(dalloc(&e->bcarry, (size_t)e->B));
     HIP_OK(dalloc(&e->bkeys_lik, (size_t)e->Mloc));
     HIP_OK(dalloc(&e->bkeys_prior, (size_t)e->Mloc));
+    if (e->chains) HIP_OK(dalloc(&e->bkeys_theta, (size_t)e->Mloc));
     HIP_OK(dalloc(&e->hp, (size_t)e->B));
     e->hp_host.assign((size_t)e->B, dibs_problem_hparams{c.alpha_linear, c.beta_linear, c.h_latent, c.stepsize, c.score_function_baseline,
                                                          c.latent_prior_std, c.graph_prior_edges_per_node});
@@ -250,6 +253,33 @@ extern "C" int dibs_engine_create(const dibs_config* cfg, void* stream, dibs_eng
   *out = nullptr;
   const dibs_config& c = *cfg;
   if (c.abi_version != DIBS_ABI_VERSION) return fail("dibs_config.abi_version mismatch");
+  {
+    // chains engine (reserved_i[2] = n_chains = C > 1, include/dibs_hip.h): C chains of one joint model on one data set, one rank, float32
+    const int64_t C = c.reserved_i[2];
+    const std::string pre = "chains engine (n_chains > 1): ";
+    if (C < 0) return fail(pre + "n_chains (reserved_i[2]) must be >= 0");
+    if (C > 1) {
+      if (c.reserved_i[0] > 1) return fail(pre + "n_problems (reserved_i[0]) must be 0 or 1 (chains share one data set; a batch of problems has no chains)");
+      if (!c.joint) return fail(pre + "marginal models are not supported (JointDiBS only; MarginalDiBS restarts are a batched engine, n_problems)");
+      if (c.n_ranks != 1) return fail(pre + "n_ranks must be 1 (chains are not sharded over ranks)");
+      if (c.reserved_i[1] == 64) return fail(pre + "float64 is not supported (the float64 engine runs MarginalDiBS + BGe only)");
+      const DibsTuning tn = dibs_tuning_from_env();
+      if (c.n_particles >= 256 || c.n_particles >= tn.kmat_t64_min)
+        return fail(pre + "n_particles (per chain) must be < 256 (the GEMM form of the SVGD transform is not batched)");
+      const int64_t rows = C * (int64_t)(c.n_particles > 0 ? c.n_particles : 1);
+      if (rows > ((int64_t)1 << 24)) return fail(pre + "n_chains * n_particles must be <= 2^24");
+      // Per-row arrays of C M rows that kernels of the standalone step address with 32-bit element offsets (or that are safe only while they
+      // stay below 2^31 elements): the packed rows, the d x d arrays and the acyclicity partial sums (at most Sa blocks per particle), the
+      // per-sample arrays, DenseNN's per-hidden-unit first-layer tables.  One rule for all of them.
+      const int64_t d = c.n_vars, k = c.n_dim > 0 ? c.n_dim : 1, lim = (int64_t)1 << 31;
+      const bool nn_ok = c.likelihood != DIBS_LIK_DENSENN || (c.nn_n_hidden >= 1 && c.nn_n_hidden <= DIBS_MAX_HIDDEN_LAYERS);  // (validated below)
+      const int64_t row_elems = 4 * d * k + 2 * (nn_ok ? theta_size(c) : 0) + 4;
+      const int64_t h0 = c.likelihood == DIBS_LIK_DENSENN && c.nn_n_hidden >= 1 && c.nn_hidden[0] > 0 ? c.nn_hidden[0] : 1;
+      const int64_t Sa = c.n_acyclicity_mc_samples > 0 ? c.n_acyclicity_mc_samples : 1, S = c.n_grad_mc_samples > 0 ? c.n_grad_mc_samples : 1;
+      if (rows * row_elems >= lim || rows * d * d * Sa >= lim || rows * d * d * h0 >= lim || rows * S >= lim)
+        return fail(pre + "n_chains * n_particles rows are too many for this model size (a per-row array would pass 2^31 elements)");
+    }
+  }
   {
     // precision (reserved_i[1]): 0 / 32 = float32, 64 = the float64 engine (MarginalDiBS + BGe + score estimator, one rank, one problem)
     const int prec = c.reserved_i[1];
@@ -366,7 +396,7 @@ extern "C" int dibs_engine_destroy(dibs_engine* e) {
   if (e->stream2) hipStreamSynchronize(e->stream2);
   void* ptrs[] = {e->z, e->vz, e->theta, e->vtheta, e->baseline, e->baseline2, e->scores, e->probs, e->eas, e->thr, e->w_lik, e->acyc_part, e->w_acyc,
                   e->logprobs_z, e->logprobs_th, e->pack, e->kz, e->kt, e->phi_z, e->phi_th, e->counters, e->masks,
-                  e->node_scores, e->x, e->mask, e->bq.list, e->bq.counts, e->soft_ds, e->acyc_big, e->w_tot, e->join_flag, e->fork_flag, e->carry_bak, e->soft_tri, e->ksum, e->kpart, e->kmat_ctr, e->bcarry, e->bkeys_lik, e->bkeys_prior, e->hp};
+                  e->node_scores, e->x, e->mask, e->bq.list, e->bq.counts, e->soft_ds, e->acyc_big, e->w_tot, e->join_flag, e->fork_flag, e->carry_bak, e->soft_tri, e->ksum, e->kpart, e->kmat_ctr, e->bcarry, e->bkeys_lik, e->bkeys_prior, e->bkeys_theta, e->hp};
   for (void* p : ptrs)
     if (p) hipFree(p);
   joint_free(&e->jw);
@@ -466,7 +496,7 @@ static ProblemHP derive_problem_hp(const dibs_engine* e, const dibs_problem_hpar
   const dibs_config c = problem_config(e, h);
   const float sigz = latent_sigma(c.latent_prior_std, e->k);
   return ProblemHP{c.alpha_linear, c.beta_linear, c.score_function_baseline, 0.f, 0.f, (float)er_log_odds(c), 1.0f / (sigz * sigz),
-                   (float)c.h_latent, (float)c.stepsize};
+                   (float)c.h_latent, (float)c.stepsize, (float)c.h_theta};
 }
 static bool same_derived(const ProblemHP& a, const ProblemHP& b) {
   return a.alpha_linear == b.alpha_linear && a.beta_linear == b.beta_linear && a.sf_baseline == b.sf_baseline && a.prior_c == b.prior_c &&
@@ -475,6 +505,7 @@ static bool same_derived(const ProblemHP& a, const ProblemHP& b) {
 
 extern "C" int dibs_engine_set_problem_hparams(dibs_engine* e, int32_t p, const dibs_problem_hparams* hp) {
   if (!e || !hp) return fail("batched engine: dibs_engine_set_problem_hparams: null engine or argument");
+  if (refuse_chains(e, "dibs_engine_set_problem_hparams (the chains share every hyper-parameter)")) return 1;
   if (e->B <= 1) return fail("batched engine: dibs_engine_set_problem_hparams needs one (dibs_config.reserved_i[0] = n_problems must be > 1)");
   if (p < 0 || p >= e->B) return fail("batched engine: dibs_engine_set_problem_hparams: problem index out of range");
   if (e->hp_final)
@@ -590,8 +621,13 @@ static int run_chunk(dibs_engine* e, int t_start, int n_steps, Step step) {
 
 extern "C" int dibs_engine_run(dibs_engine* e, int32_t t_start, int32_t n_steps) {
   if (!e) return fail("null engine");
-  if (e->B > 1 && !e->has_data) return fail("dibs_engine_set_data_problem has not been called for every problem");
+  if (e->B > 1 && !e->chains && !e->has_data) return fail("dibs_engine_set_data_problem has not been called for every problem");
   if (!e->has_data) return fail("dibs_engine_set_data has not been called");
+  if (e->chains) {
+    HIP_OK(hipSetDevice(e->cfg.device_id));
+    if (batch_hp_commit(e)) return 1;
+    return run_chunk(e, t_start, n_steps, [e](int t) { return step_chains(e, t); });
+  }
   if (e->B > 1) {
     HIP_OK(hipSetDevice(e->cfg.device_id));
     if (batch_hp_commit(e)) return 1;

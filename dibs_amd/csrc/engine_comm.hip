@@ -87,6 +87,7 @@ extern "C" int dibs_engine_comm_destroy(dibs_engine* e) {
 
 extern "C" int dibs_engine_comm_init(dibs_engine* e, const void* ids, int32_t n_ids) {
   if (!e) return fail("null argument");
+  if (refuse_chains(e, "the sharded entry points (chains are not sharded over ranks)")) return 1;
   if (e->B > 1) return fail("batched engine: a batch is not sharded over ranks");
   if (n_ids < 1 || n_ids > 2) return fail("n_ids must be 1 (one all-gather per step) or 2 (overlapped exchange as well)");
   // ids == NULL: LOOPBACK -- no communicator, the all-gathers are skipped and the rows of the other ranks keep whatever the buffers hold.
@@ -122,6 +123,7 @@ static_assert(DIBS_IPC_HANDLE_BYTES == sizeof(IpcBlob), "include/dibs_hip.h: DIB
 // allocates this rank's exchange arena (zeroed: no exchange has arrived) and writes the blob its peers need to map it
 extern "C" int dibs_engine_ipc_export(dibs_engine* e, void* blob_out) {
   if (!e || !blob_out) return fail("null argument");
+  if (refuse_chains(e, "the sharded entry points (chains are not sharded over ranks)")) return 1;
   if (e->B > 1) return fail("batched engine: a batch is not sharded over ranks");
   if (e->cfg.n_ranks > IPC_MAX_RANKS) return fail("the mapped-memory exchange supports at most " + std::to_string(IPC_MAX_RANKS) + " ranks");
   HIP_OK(hipSetDevice(e->cfg.device_id));
@@ -327,6 +329,7 @@ static int agree_on_error(dibs_engine* e, unsigned int mine, unsigned int* any) 
 extern "C" int dibs_engine_run_sharded(dibs_engine* e, int32_t t_start, int32_t n_steps, int32_t overlapped) {
   if (!e) return fail("null engine");
   if (e->f64) return fail("float64 engine: dibs_engine_run_sharded is not supported (dibs_engine_run only)");
+  if (refuse_chains(e, "the sharded entry points (chains are not sharded over ranks)")) return 1;
   if (e->B > 1) return fail("batched engine: a batch is not sharded over ranks");
   if (!e->has_data) return fail("dibs_engine_set_data has not been called");
   if (e->n_comms < 1) return fail("dibs_engine_comm_init has not been called");

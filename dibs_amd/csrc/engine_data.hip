@@ -164,7 +164,7 @@ static int bge_prepare(BgeStats* st, const dibs_config& cfg, int d, int N, const
 
 extern "C" int dibs_engine_set_data(dibs_engine* e, const float* x, const int32_t* interv_mask, const float* bge_mean_obs) {
   if (!e || !x) return fail("null argument");
-  if (e->B > 1) return fail("batched engine: use dibs_engine_set_data_problem");
+  if (e->B > 1 && !e->chains) return fail("batched engine: use dibs_engine_set_data_problem");
   if (e->f64) {  // float64 engine: the data widened exactly
     const size_t n = (size_t)e->N * e->d;
     std::vector<double> x64(x, x + n), mo64;
@@ -200,6 +200,7 @@ extern "C" int dibs_engine_set_data(dibs_engine* e, const float* x, const int32_
 // ---- batched engine: data per problem (include/dibs_hip.h, n_problems) ----------------------------------------------------
 extern "C" int dibs_engine_set_data_problem(dibs_engine* e, int32_t p, const float* x, int32_t n_obs, const int32_t* interv_mask,
                                             const float* bge_mean_obs) {
+  if (refuse_chains(e, "dibs_engine_set_data_problem (the chains share one data set: dibs_engine_set_data)")) return 1;
   if (need_batch(e)) return 1;
   if (!x) return fail("null argument");
   if (p < 0 || p >= e->B) return fail("problem index out of range");
@@ -265,6 +266,7 @@ extern "C" int dibs_score_graphs(dibs_engine* e, const int32_t* g, const float* 
                                  const int32_t* mask_ho, int32_t n_ho, float* out) {
   if (!e || !g || !x_ho || !out) return fail("null argument");
   if (e->f64) return fail("float64 engine: dibs_score_graphs is not supported (dibs_engine_run only)");
+  if (refuse_chains(e, "dibs_score_graphs (score with a standalone engine)")) return 1;
   if (e->B > 1) return fail("batched engine: dibs_score_graphs is not supported (score with a standalone engine)");
   if (n <= 0) return 0;
   HIP_OK(hipSetDevice(e->cfg.device_id));

@@ -82,6 +82,10 @@ struct dibs_engine {
   int B = 1;
   Key2* bcarry = nullptr;                             // [B] loop-carry keys, advanced on the device (k_batch_keys)
   Key2 *bkeys_lik = nullptr, *bkeys_prior = nullptr;  // [B * M] this step's per-particle keys
+  // chains engine (cfg.reserved_i[2] = n_chains = C > 1): C chains of ONE joint model on ONE data set.  B = C and the rows are laid out as
+  // a batched engine's (chain-major, M = one chain's particles); the data and every hyper-parameter are shared.  See step_chains.
+  bool chains = false;
+  Key2* bkeys_theta = nullptr;                        // [C * M] this step's keys of the theta estimator (k_chain_keys)
   // per-problem hyper-parameters (dibs_engine_set_problem_hparams): the host values, and the device table of what the kernels take from
   // them (ProblemHP, common.h), written ONCE by batch_hp_commit when the particles are initialised -- set_problem_hparams is refused from
   // then on.  hp_tier: the step's kernels read the table (n_vars, n_dim <= 64 and what else batch_hp_tier asks); otherwise only the
@@ -214,6 +218,10 @@ inline int need_batch(const dibs_engine* e) {
   if (e->B <= 1) return fail("not a batched engine (dibs_config.reserved_i[0] = n_problems must be > 1)");
   return 0;
 }
+// chains engine: the entry points it has no form of
+inline int refuse_chains(const dibs_engine* e, const char* what) {
+  return e && e->chains ? fail(std::string("chains engine (n_chains > 1): ") + what + " is not supported") : 0;
+}
 
 // Erdos-Renyi graph prior: the edge probability of the configuration, and its log odds (0 for the other priors)
 inline double er_edge_prob(const dibs_config& c) { return c.graph_prior_edges_per_node * c.n_vars / ((c.n_vars * (c.n_vars - 1)) / 2.0); }
@@ -329,6 +337,7 @@ int join_failure(unsigned int code, const char* what);
 int step_local(dibs_engine* e, int t, const RowTarget& rt, const StepKeys* xk = nullptr, int terms = TERMS_ALL, const float* zero_w = nullptr);
 int step_update(dibs_engine* e, int t, const RowSource& rs, float* vals_send = nullptr);
 int step_batch(dibs_engine* e, int t);
+int step_chains(dibs_engine* e, int t);
 int carry_copy(dibs_engine* e, bool restore);
 void launch_stream_probe(hipStream_t main_stream, hipStream_t second_stream, unsigned int* words);  // k_probe_wait / k_probe_set (engine_alloc)
 // ---- tu_batch.hip: the table-reading launches of step_batch (n_vars, n_dim <= 64; dibs_engine::hp_tier) ----
@@ -336,6 +345,10 @@ void batch_launch_edge_scores(hipStream_t st, const float* z, float* scores, uin
                               int Mloc, int d, int k, int dpad, int ldk);
 void batch_launch_tail(hipStream_t st, const TailArgs& ta, const ProblemHP* hp, int pM, int Mloc, size_t lds);
 void batch_launch_acyc_power(const AcycLaunch& a, const ProblemHP* hp, int pM);
+// ---- tu_batch.hip: the chain-aware launches of step_chains (keys, block-diagonal kernel matrices) ----
+void chains_launch_keys(hipStream_t st, Key2* carry, Key2* keys_theta, Key2* keys_lik, Key2* keys_prior, int C, int M, int layout);
+void chains_launch_kmat(hipStream_t st, bool tiled, const float* x, size_t len, float* kout, int C, int M, float scale, float h, const float* kadd,
+                        float* ksum, size_t lds_direct);
 // ---- engine_f64.hip ----
 int f64_alloc(dibs_engine* e);
 int f64_init_particles(dibs_engine* e, Key2 isub);

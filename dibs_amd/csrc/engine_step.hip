@@ -12,6 +12,7 @@ void launch_stream_probe(hipStream_t main_stream, hipStream_t second_stream, uns
 
 extern "C" int dibs_engine_init_particles(dibs_engine* e, const uint32_t key[2]) {
   if (!e || !key) return fail("null argument");
+  if (e->chains) return fail("chains engine (n_chains > 1): use dibs_engine_init_particles_batch (one key per chain)");
   if (e->B > 1) return fail("batched engine: use dibs_engine_init_particles_batch");
   HIP_OK(hipSetDevice(e->cfg.device_id));
   const int L = e->cfg.rng_layout;
@@ -64,9 +65,22 @@ extern "C" int dibs_engine_init_particles_batch(dibs_engine* e, const uint32_t* 
     const Key2 isub = rng_split_row(subk, 2, 1, L);
     hipLaunchKernelGGL(k_init_z, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, e->z + (size_t)p * n, isub, n, (uint64_t)0, n,
                        latent_sigma(e->hp_host[(size_t)p].latent_prior_std, e->k), L);
+    if (e->chains) {  // (chain p's parameters: the launch of dibs_engine_init_particles for a joint model, rows p M .. p M + M - 1)
+      const Key2 ikey = rng_split_row(subk, 2, 0, L);
+      const Key2 tsub = rng_split_row(ikey, 2, 1, L);
+      float* const th = e->theta + (size_t)p * e->M * e->P;
+      if (e->cfg.likelihood == DIBS_LIK_LINGAUSS) {
+        const uint64_t tt = (uint64_t)e->M * e->P;
+        hipLaunchKernelGGL(k_init_theta_lin, dim3((unsigned)((tt + 255) / 256)), dim3(256), 0, e->stream, th, tsub, tt, (uint64_t)0, tt,
+                           (float)e->cfg.lin_mean_edge, (float)e->cfg.lin_sig_edge, (float)e->cfg.lin_min_edge, L);
+      } else {
+        joint_nn_init_theta(th, (size_t)e->P, tsub, 0, e->M, e->M, e->d, nn_params(e->cfg), L, e->stream);
+      }
+    }
   }
   HIP_OK(hipMemcpyAsync(e->bcarry, carry.data(), carry.size() * sizeof(Key2), hipMemcpyHostToDevice, e->stream));
   HIP_OK(hipMemsetAsync(e->vz, 0, (size_t)e->Mloc * e->D * 4, e->stream));
+  if (e->chains) HIP_OK(hipMemsetAsync(e->vtheta, 0, (size_t)e->Mloc * e->P * 4, e->stream));
   HIP_OK(hipMemsetAsync(e->baseline, 0, (size_t)e->Mloc * 4, e->stream));
   HIP_OK(hipGetLastError());
   HIP_OK(hipStreamSynchronize(e->stream));
@@ -310,7 +324,8 @@ static void launch_phi_update(dibs_engine* e, const float* pack, size_t stride, 
                        (int)cols, ngroups, vals_send, vals_stride, s.is_theta ? (size_t)e->D : (size_t)0);                                 \
   }
 #define PHI_PICK(TA_)                                                                                                                      \
-  if (e->B > 1) { if (full) PHI_LAUNCH(TA_, true, false, true) else PHI_LAUNCH(TA_, false, false, true) }                                  \
+  if (e->B > 1 && e->kt) { if (full) PHI_LAUNCH(TA_, true, true, true) else PHI_LAUNCH(TA_, false, true, true) }                           \
+  else if (e->B > 1) { if (full) PHI_LAUNCH(TA_, true, false, true) else PHI_LAUNCH(TA_, false, false, true) }                             \
   else if (e->kt) { if (full) PHI_LAUNCH(TA_, true, true, false) else PHI_LAUNCH(TA_, false, true, false) }                                \
   else { if (full) PHI_LAUNCH(TA_, true, false, false) else PHI_LAUNCH(TA_, false, false, false) }
   if (ta == 16) { PHI_PICK(16) } else if (ta == 8) { PHI_PICK(8) } else { PHI_PICK(4) }
@@ -676,10 +691,84 @@ int step_batch(dibs_engine* e, int t) {
   return 0;
 }
 
+// ---- chains engine (n_chains = C > 1, include/dibs_hip.h) ------------------------------------------------------------------------------
+// One step of C chains of one joint model on one data set in the launches of one standalone step: rows [C * M] chain-major.  The data is
+// shared, so every kernel that reads it -- and the edge, acyclicity and tail kernels -- runs unchanged over all rows, with explicit keys
+// (Mg = -1, rng_explicit_row) that k_chain_keys derives from the C device-resident carries.  Chain-aware: the keys, the two block-diagonal
+// kernel matrices [C * M][M] (latent -> kz, theta -> kt and kz + kt -> ksum) and the SVGD transform (k_phi_update's JOINT + BATCH forms,
+// grid.y = chain).  Fork / join of the second stream by events only; every choice a standalone engine makes from its particle count is
+// made from M, one chain's (acyc_cpb, the kernel-matrix algorithm, phi's TA / FULL, JointLaunch::M_choice), never from C * M.
+static bool chains_kmat_tiled(const dibs_engine* e) {  // (kmat_tiled_on of a standalone engine of M particles)
+  return e->M >= e->tune.kmat_tiled_min && kmat_tile_addressable((size_t)2 * e->M, e->E > e->Ev ? e->E : e->Ev, 0, 0);
+}
+int step_chains(dibs_engine* e, int t) {
+  const dibs_config& c = e->cfg;
+  const float alpha = (float)(c.alpha_linear * t), beta = (float)(c.beta_linear * t);
+  chains_launch_keys(e->stream, e->bcarry, e->bkeys_theta, e->bkeys_lik, e->bkeys_prior, e->B, e->M, c.rng_layout);
+  const Key2 carry_theta = key_array_as_carry(e->bkeys_theta, 0), carry_lik = key_array_as_carry(e->bkeys_lik, 0),
+             carry_prior = key_array_as_carry(e->bkeys_prior, 0);
+  launch_edge_scores(e, e->stream, alpha, EdgeFork{}, nullptr);
+  // acyclicity term and both kernel matrices on the second stream (they need only this step's scores / z / theta), the estimators on the first
+  const EventFork ef(e);
+  if (ef.fork()) return 1;
+  launch_acyc(e, ef.s2, carry_prior, -1, alpha);
+  {
+    KTimer tm(e, DIBS_K_KMAT, ef.s2);
+    const bool tiled = chains_kmat_tiled(e);
+    chains_launch_kmat(ef.s2, tiled, e->z, (size_t)e->D, e->kz, e->B, e->M, (float)c.scale_latent, (float)c.h_latent, nullptr, nullptr,
+                       kmat_lds_bytes((size_t)e->D));
+    chains_launch_kmat(ef.s2, tiled, e->theta, (size_t)e->P, e->kt, e->B, e->M, (float)c.scale_theta, (float)c.h_theta, e->kz, e->ksum,
+                       kmat_lds_bytes((size_t)e->P));
+  }
+  if (ef.chain_done()) return 1;
+  const RowTarget rt = packed_rows(e, e->pack);
+  JointLaunch jl = joint_launch_args(e, rt, -1, alpha);
+  jl.M_choice = e->M;
+  const char* const scratch = ": scratch area: hipMalloc failed, or the partial sums of all chains pass the gradient kernel's addressing limit";
+  if (c.likelihood == DIBS_LIK_LINGAUSS) {
+    jl.obs_noise = (float)c.lin_obs_noise;
+    jl.mean_edge = (float)c.lin_mean_edge;
+    jl.sig_edge = (float)c.lin_sig_edge;
+    {
+      KTimer tm(e, DIBS_K_LIN_THETA);
+      if (joint_lin_all_logprobs(&e->jw, jl, carry_theta, carry_lik)) return fail(std::string("chains engine (n_chains > 1): LinearGaussian") + scratch);
+    }
+    {
+      KTimer tm(e, DIBS_K_LIN_Z);
+      if (joint_lin_all_grads(&e->jw, jl, carry_theta, carry_lik)) return fail(std::string("chains engine (n_chains > 1): LinearGaussian") + scratch);
+    }
+  } else {
+    const NNParams np_ = nn_params(c);
+    {
+      KTimer tm(e, DIBS_K_NN_THETA);
+      if (joint_nn_dispatch(&e->jw, jl, carry_theta, LIN_MODE_THETA, np_, (size_t)e->P))
+        return fail(std::string("chains engine (n_chains > 1): DenseNonlinearGaussian") + scratch);
+    }
+    {
+      KTimer tm(e, DIBS_K_NN_Z);
+      if (joint_nn_dispatch(&e->jw, jl, carry_lik, c.grad_estimator_z == 0 ? LIN_MODE_Z_SCORE : LIN_MODE_Z_REPARAM, np_, (size_t)e->P))
+        return fail(std::string("chains engine (n_chains > 1): DenseNonlinearGaussian") + scratch);
+    }
+  }
+  std::swap(e->baseline, e->baseline2);
+  if (ef.join()) return 1;
+  launch_tail(e, rt, TailOpts{alpha, beta, false, true, e->w_lik, false, nullptr, false});
+  {
+    KTimer tm(e, DIBS_K_PHI_UPDATE);
+    launch_phi_update(e, e->pack, (size_t)e->E, PhiSeg{0, (size_t)e->D, (size_t)e->D, 0, e->z, e->vz, e->phi_z, (float)c.h_latent}, e->M, nullptr, 0);
+    launch_phi_update(e, e->pack, (size_t)e->E, PhiSeg{(size_t)(2 * e->D), (size_t)(2 * e->D + e->P), (size_t)e->P, 1, e->theta, e->vtheta, e->phi_th,
+                                                       (float)c.h_theta}, e->M, nullptr, 0);
+  }
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(err));
+  return 0;
+}
+
 // ---- the entry points of a loop driven from outside (include/dibs_hip.h) ----------------------------------------------------------------
 extern "C" int dibs_engine_step_local(dibs_engine* e, int32_t t, void* send_dev) {
   if (!e || !send_dev) return fail("null argument");
   if (e->f64) return fail("float64 engine: dibs_engine_step_local is not supported (dibs_engine_run only)");
+  if (refuse_chains(e, "dibs_engine_step_local (only dibs_engine_run steps it)")) return 1;
   if (e->B > 1) return fail("batched engine: only dibs_engine_run steps it");
   if (!e->has_data) return fail("dibs_engine_set_data has not been called");
   HIP_OK(hipSetDevice(e->cfg.device_id));
@@ -695,6 +784,7 @@ extern "C" int64_t dibs_engine_plane_elems_per_rank(const dibs_engine* e) { retu
 extern "C" int dibs_engine_export_values(dibs_engine* e, void* vals_send_dev) {
   if (!e || !vals_send_dev) return fail("null argument");
   if (e->f64) return fail("float64 engine: dibs_engine_export_values is not supported (dibs_engine_run only)");
+  if (refuse_chains(e, "dibs_engine_export_values")) return 1;
   HIP_OK(hipSetDevice(e->cfg.device_id));
   float* dst = (float*)vals_send_dev;
   HIP_OK(hipMemcpy2DAsync(dst, (size_t)e->Ev * 4, e->z, (size_t)e->D * 4, (size_t)e->D * 4, (size_t)e->Mloc, hipMemcpyDeviceToDevice, e->stream));
@@ -707,6 +797,7 @@ extern "C" int dibs_engine_export_values(dibs_engine* e, void* vals_send_dev) {
 extern "C" int dibs_engine_step_local_grads(dibs_engine* e, int32_t t, void* grads_send_dev) {
   if (!e || !grads_send_dev) return fail("null argument");
   if (e->f64) return fail("float64 engine: dibs_engine_step_local_grads is not supported (dibs_engine_run only)");
+  if (refuse_chains(e, "dibs_engine_step_local_grads (only dibs_engine_run steps it)")) return 1;
   if (e->B > 1) return fail("batched engine: only dibs_engine_run steps it");
   if (!e->has_data) return fail("dibs_engine_set_data has not been called");
   HIP_OK(hipSetDevice(e->cfg.device_id));
@@ -722,6 +813,7 @@ extern "C" int dibs_engine_step_local_grads(dibs_engine* e, int32_t t, void* gra
 extern "C" int dibs_engine_kmat_values(dibs_engine* e, const void* vals_all_dev, void* stream) {
   if (!e || !vals_all_dev || !stream) return fail("null argument");
   if (e->f64) return fail("float64 engine: dibs_engine_kmat_values is not supported (dibs_engine_run only)");
+  if (refuse_chains(e, "dibs_engine_kmat_values (only dibs_engine_run steps it)")) return 1;
   if (e->B > 1) return fail("batched engine: only dibs_engine_run steps it");
   HIP_OK(hipSetDevice(e->cfg.device_id));
   const float* vals = (const float*)vals_all_dev;
@@ -734,6 +826,7 @@ extern "C" int dibs_engine_kmat_values(dibs_engine* e, const void* vals_all_dev,
 extern "C" int dibs_engine_step_update_planes(dibs_engine* e, int32_t t, const void* planes_dev, void* vals_send_dev) {
   if (!e || !planes_dev) return fail("null argument");
   if (e->f64) return fail("float64 engine: dibs_engine_step_update_planes is not supported (dibs_engine_run only)");
+  if (refuse_chains(e, "dibs_engine_step_update_planes (only dibs_engine_run steps it)")) return 1;
   if (e->B > 1) return fail("batched engine: only dibs_engine_run steps it");
   HIP_OK(hipSetDevice(e->cfg.device_id));
   return step_update(e, t, plane_source(e, (const float*)planes_dev), (float*)vals_send_dev);
@@ -742,6 +835,7 @@ extern "C" int dibs_engine_step_update_planes(dibs_engine* e, int32_t t, const v
 extern "C" int dibs_engine_step_update(dibs_engine* e, int32_t t, const void* recv_dev) {
   if (!e || !recv_dev) return fail("null argument");
   if (e->f64) return fail("float64 engine: dibs_engine_step_update is not supported (dibs_engine_run only)");
+  if (refuse_chains(e, "dibs_engine_step_update (only dibs_engine_run steps it)")) return 1;
   if (e->B > 1) return fail("batched engine: only dibs_engine_run steps it");
   HIP_OK(hipSetDevice(e->cfg.device_id));
   return step_update(e, t, packed_source(e, (const float*)recv_dev));
@@ -753,6 +847,7 @@ extern "C" int dibs_engine_eval_gradients(dibs_engine* e, int32_t t, const uint3
                                           float* grad_z_lik, float* baseline_out, float* grad_theta, float* grad_z_prior) {
   if (!e) return fail("null engine");
   if (e->f64) return fail("float64 engine: dibs_engine_eval_gradients is not supported (dibs_engine_run only)");
+  if (refuse_chains(e, "dibs_engine_eval_gradients")) return 1;
   if (e->B > 1) return fail("batched engine: dibs_engine_eval_gradients is not supported");
   if (!e->has_data) return fail("dibs_engine_set_data has not been called");
   const dibs_config& c = e->cfg;

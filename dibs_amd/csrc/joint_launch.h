@@ -81,6 +81,10 @@ struct JointLaunch {
   double sf_baseline;
   float obs_noise, mean_edge, sig_edge;
   int lin_f32 = 0, nn_f32 = 0;  // the engine's DibsTuning (tuning.h): keep the f32-MFMA log-probability kernels (A/B runs)
+  // chains engine (include/dibs_hip.h, n_chains): the particle count the launchers size their blocks from (samples per block, blocks per
+  // particle) is one chain's, so that a chain is launched as its standalone engine would launch it; 0: Mloc
+  int M_choice = 0;
+  int choice_rows() const { return M_choice > 0 ? M_choice : Mloc; }
 };
 
 struct NNParams {

@@ -259,7 +259,7 @@ __host__ __device__ inline size_t phi_update_lds_bytes(int TA, int M) {
 // FULL: M is a multiple of 64, i.e. every wave's quarter is a whole number of 8-pair batches, whole particle groups, buffer < 4 GiB -- no
 // clamps, no per-pair tests, buffer loads (the headline size, configs 3 and 4); otherwise rows past a quarter repeat its last row and meet zero
 // kernel entries.  JOINT: a second kernel matrix (theta), weights ks = kz + kt and the repulsion of the segment's own kernel.
-// BATCH (batched engines, include/dibs_hip.h n_problems): blockIdx.y = problem p; its M rows of pack / x / v / phi_out and its block
+// BATCH (batched engines, include/dibs_hip.h n_problems; with JOINT the chains engine, n_chains): blockIdx.y = problem p; its M rows of pack / x / v / phi_out and its block
 // [M][M] of the block-diagonal kernel matrix are the whole input of a standalone launch (m0 = 0, Mloc = M): the same sums in the same order.
 // bandwidth and step size of a launch: two float arguments, as ever; the BATCH instantiations take the per-problem table (common.h) in the
 // place of the first and nothing (an int that is not read) in the place of the second
@@ -286,14 +286,15 @@ __global__ __launch_bounds__(256) void k_phi_update(const float* __restrict__ pa
     stepsize = stepsize_arg;
   }
   if constexpr (BATCH) {
-    static_assert(!JOINT, "batched engines run the marginal model only");
     const size_t p = blockIdx.y;
     pack += p * (size_t)M * pack_stride;
     kz += p * (size_t)M * M;
+    if constexpr (JOINT) kt += p * (size_t)M * M;  // (chains engine: both matrices are block-diagonal, one [M][M] block per chain)
     x += p * (size_t)M * len;
     v += p * (size_t)M * len;
     if (phi_out) phi_out += p * (size_t)M * len;
     h = h_arg[p].h;  // (the problem's own bandwidth and step size)
+    if constexpr (JOINT) h = seg_is_theta ? h_arg[p].h_theta : h;  // (the bandwidth of the segment's own kernel)
     stepsize = h_arg[p].stepsize;
   }
   typedef float f32x2 __attribute__((ext_vector_type(2)));

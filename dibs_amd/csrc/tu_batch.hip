@@ -1,6 +1,7 @@
 // translation unit: the table-reading kernels of the batched engine (include/dibs_hip.h, dibs_engine_set_problem_hparams; ProblemHP in
 // common.h) and their launchers.  Each is the block of a standalone kernel under a __global__ that takes the scalar(s) of the block's problem
 // from the per-problem table.  A unit of their own, so that the units of the standalone kernels compile what they compiled without them.
+// Further down: the chain-aware kernels of the chains engine (n_chains; keys, block-diagonal kernel matrices) and their launchers.
 #define DIBS_TU_BATCH
 #include "engine_impl.h"
 #include "kernels_edge_p.h"
@@ -65,4 +66,68 @@ void batch_launch_acyc_power(const AcycLaunch& a, const ProblemHP* hp, int pM) {
     case 3: launch_nt_batch<3>(a, hp, pM); break;
     default: launch_nt_batch<4>(a, hp, pM); break;
   }
+}
+
+// ---- chains engine (include/dibs_hip.h: n_chains = C > 1; rows [C * M], chain-major, ONE joint model on ONE data set) -------------------
+// per-chain keys of one step from the C device-resident loop-carry keys, in the order of step_local for a joint model (svgd.py:695-703 per
+// chain): carry_theta = carry, carry_lik = row 0 of split(carry_theta, M + 1), carry_prior = row 0 of split(carry_lik, M + 1), and the carry
+// advances to row 0 of split(carry_prior, M + 1); particle m's key of an estimator is row 1 + m of that estimator's split.  grid = C
+__global__ __launch_bounds__(256) void k_chain_keys(Key2* __restrict__ carry, Key2* __restrict__ keys_theta, Key2* __restrict__ keys_lik,
+                                                    Key2* __restrict__ keys_prior, int M, int layout) {
+  const int p = blockIdx.x;
+  const uint32_t n = (uint32_t)M + 1u;
+  const Key2 c_theta = carry[p];
+  const Key2 c_lik = rng_split_row(c_theta, n, 0u, layout);
+  const Key2 c_prior = rng_split_row(c_lik, n, 0u, layout);
+  for (int m = threadIdx.x; m < M; m += blockDim.x) {
+    const size_t o = (size_t)p * M + m;
+    keys_theta[o] = rng_split_row(c_theta, n, (uint32_t)m + 1u, layout);
+    keys_lik[o] = rng_split_row(c_lik, n, (uint32_t)m + 1u, layout);
+    keys_prior[o] = rng_split_row(c_prior, n, (uint32_t)m + 1u, layout);
+  }
+  __syncthreads();  // (every thread has read carry[p])
+  if (threadIdx.x == 0) carry[p] = rng_split_row(c_prior, n, 0u, layout);
+}
+void chains_launch_keys(hipStream_t st, Key2* carry, Key2* keys_theta, Key2* keys_lik, Key2* keys_prior, int C, int M, int layout) {
+  hipLaunchKernelGGL(k_chain_keys, dim3(C), dim3(256), 0, st, carry, keys_theta, keys_lik, keys_prior, M, layout);
+}
+
+// block-diagonal kernel matrix of one segment (z or theta), kout [C * M][M]: row a of chain p = a / M against the M particles of p only, by
+// the code of the standalone launch (kmat_block, symmetric) -- bit-identical entries; ksum != null: kadd + k as well (the weight matrix
+// kz + kt of the SVGD transform).  grid = (C * M, ceil(M / KMAT_BT))
+__global__ __launch_bounds__(256) void k_kmat_chains(const float* __restrict__ x, size_t stride, int len, float* __restrict__ kout, int M,
+                                                     float scale, float h, const float* __restrict__ kadd, float* __restrict__ ksum) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int a = blockIdx.x, p = a / M;
+  const size_t ko = (size_t)p * M * M;
+  kmat_block(smem, x + (size_t)p * M * stride, stride, 0, len, kout + ko, 0, M, scale, h, 1, a - p * M, blockIdx.y, kadd ? kadd + ko : nullptr,
+             ksum ? ksum + ko : nullptr);
+}
+// ... the tiled form (standalone engines from DibsTuning::kmat_tiled_min particles): blockIdx.y = chain, one piece per tile (nsplit = 1: the
+// entries do not depend on the cut, see KmatTile).  kt describes chain 0
+__global__ __launch_bounds__(KT_NT) void k_kmat_tile_chains(KmatTile kt) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const size_t p = blockIdx.y, ko = p * (size_t)kt.M * kt.M;
+  KmatTile k = kt;
+  k.x = kt.x + p * (size_t)kt.M * kt.stride;
+  k.kout = kt.kout + ko;
+  if (kt.ksum) {
+    k.kadd = kt.kadd + ko;
+    k.ksum = kt.ksum + ko;
+  }
+  kmat_tile_block(smem, k, (int)blockIdx.x, (int)gridDim.x, (int)threadIdx.x);
+}
+// one segment's matrix of every chain on `st`; `tiled`: the choice of a standalone engine of M particles (made by the caller from M alone)
+void chains_launch_kmat(hipStream_t st, bool tiled, const float* x, size_t len, float* kout, int C, int M, float scale, float h, const float* kadd,
+                        float* ksum, size_t lds_direct) {
+  if (tiled) {
+    const int nta = (M + KT_T - 1) / KT_T, tiles = kmat_tile_count(nta, nta, 1), nchunk = kmat_nchunk((int)len);
+    const KmatTile kt{x, len, 0, (int)len, nullptr, 0, M, M, nchunk, nta, nta, 1, 1, nchunk, scale, h, kout, kadd, ksum, nullptr};
+    dibs_allow_lds((const void*)k_kmat_tile_chains, kmat_tile_lds_bytes());
+    hipLaunchKernelGGL(k_kmat_tile_chains, dim3((unsigned)tiles, (unsigned)C), dim3(KT_NT), kmat_tile_lds_bytes(), st, kt);
+    return;
+  }
+  dibs_allow_lds((const void*)k_kmat_chains, lds_direct);
+  hipLaunchKernelGGL(k_kmat_chains, dim3((unsigned)(C * M), (unsigned)((M + KMAT_BT - 1) / KMAT_BT)), dim3(256), lds_direct, st, x, len, (int)len, kout, M,
+                     scale, h, kadd, ksum);
 }

@@ -168,7 +168,7 @@ static int joint_lin_logprobs(JointWork* w, const JointLaunch& jl, Key2 carry, i
     const bool use_bf = NT <= 4 && jl.d > 32 && !jl.lin_f32;  // (lin_f32: tuning.h, the f32-MFMA kernel at 33 <= d <= 64 for A/B runs)
     // pairs per block: the block's prologue (x fragments, operand factors, zeroed images) is ~a third of a pair's work; 8 pairs when that
     // still leaves two full rounds of blocks (config 3: 1 914 -> 1 964 steps/s; 16 pairs: 1 856)
-    const int ppb = (use_bf && (jl.S / 2 / 8) * jl.Mloc >= 1024) ? 8 : 4;
+    const int ppb = (use_bf && (jl.S / 2 / 8) * jl.choice_rows() >= 1024) ? 8 : 4;
     const size_t ldsp = lin_lds_bytes_pair(jl.d, NT);
     const dim3 grid((jl.S / 2 + ppb - 1) / ppb, jl.Mloc);
     const int epq = (jl.d * jl.d + 255) / 256;
@@ -242,7 +242,7 @@ int joint_lin_all_logprobs(JointWork* w, const JointLaunch& jl, Key2 carry_theta
     const int ng = glob ? (w->n_gram == 1 ? -1 : w->n_gram) : ling_ngram_arg(jl.d, w->n_gram, false);
     const size_t lds = glob ? 256 : ling_lds(jl.d, ng, false);
     // (global operands: a bounded number of blocks per particle loop over the samples, each with its own d x d scratch)
-    const int gx = glob ? (jl.S < 1024 / jl.Mloc ? jl.S : (1024 / jl.Mloc > 1 ? 1024 / jl.Mloc : 1)) : jl.S;
+    const int rows = jl.choice_rows(), gx = glob ? (jl.S < 1024 / rows ? jl.S : (1024 / rows > 1 ? 1024 / rows : 1)) : jl.S;
     float* gs = glob ? joint_gs_scratch(w, (size_t)gx * jl.Mloc * jl.d * jl.d) : nullptr;
     if (glob && !gs) return 1;
     allow_lds(k_ling_logprobs, lds);

@@ -20,7 +20,7 @@ static bool joint_nn_logprobs_hf(JointWork* w, const JointLaunch& jl, Key2 carry
     const size_t lds = nhf_lds_bytes(jl.d, NT, np_.H, soft);
     if (mode == LIN_MODE_THETA) w->nhf_valid = w->nhx_valid = false;  // (theta moved since the last step)
     if (off || !paired || jl.N > 128 || !w->ln_tab) return false;
-    const int hS = jl.S / 2, ppb = (hS / 4) * jl.Mloc >= 1024 ? 4 : (hS >= 2 ? 2 : 1);
+    const int hS = jl.S / 2, ppb = (hS / 4) * jl.choice_rows() >= 1024 ? 4 : (hS >= 2 ? 2 : 1);
     if (!w->nhf_ew && hipMalloc((void**)&w->nhf_ew, (size_t)jl.Mloc * 4) != hipSuccess) {
       (void)hipGetLastError();
       w->nhf_ew = nullptr;
@@ -113,7 +113,7 @@ template <int NT>
 static int joint_nn_launch(JointWork* w, const JointLaunch& jl, Key2 carry, int mode, const NNParams& np_, size_t P) {
   // samples per block: the block's prologue (x and the small leaves into LDS, validity bits) is shared by them; 4 while that leaves at least
   // four rounds of blocks (config 5: spb 2 / 4 / 8 -> 51.2 / 53.0 / 53.1 steps/s)
-  const int spb = (jl.S / 4) * jl.Mloc >= 1024 ? 4 : 2;
+  const int spb = (jl.S / 4) * jl.choice_rows() >= 1024 ? 4 : 2;
   const size_t lds1 = nn_lds_bytes_logprobs(jl.d, jl.N, NT, np_.H);
   float* lp = mode == LIN_MODE_THETA ? jl.logprobs_th : jl.logprobs_z;
   const size_t w1t_need = (size_t)jl.Mloc * np_.H * jl.d * jl.d;
@@ -157,7 +157,9 @@ static int joint_nn_launch(JointWork* w, const JointLaunch& jl, Key2 carry, int 
   const size_t row_theta = (size_t)NT * nudm * np_.H * 4 * nthr + (P - (size_t)jl.d * jl.d * np_.H);
   const size_t row = row_theta > (size_t)jl.d * jl.d ? row_theta : (size_t)jl.d * jl.d;
   int ns_nn = GRAD_NS_NN;
-  while (ns_nn > 1 && (size_t)jl.Mloc * ns_nn * row * 4 > ((size_t)4 << 30)) ns_nn >>= 1;
+  while (ns_nn > 1 && (size_t)jl.choice_rows() * ns_nn * row * 4 > ((size_t)4 << 30)) ns_nn >>= 1;
+  // (chains engine: the shares are one chain's, so that its sums are grouped as its standalone engine groups them; all chains' rows must fit)
+  if (jl.M_choice > 0 && (size_t)jl.Mloc * ns_nn * row * 4 > ((size_t)4 << 30)) return 1;
   if (!joint_grad_split(w, (size_t)jl.Mloc, row, &gs, ns_nn)) return 1;
   GradPlan gp;
   if (!joint_grad_plan(w, (size_t)jl.Mloc, ns_nn, &gp)) return 1;
@@ -221,7 +223,10 @@ static int joint_nng_launch(JointWork* w, const JointLaunch& jl, Key2 carry, int
   // rows within 2 GiB
   int ns_g = GRAD_NS;
   const size_t rec = (size_t)2 * net.hsum * jl.d * jl.N, row = (size_t)net.P > (size_t)jl.d * jl.d ? (size_t)net.P : (size_t)jl.d * jl.d;
-  while (ns_g > 1 && ((size_t)jl.Mloc * ns_g * rec * 4 > ((size_t)2 << 30) || (size_t)jl.Mloc * ns_g * row * 4 > ((size_t)2 << 30))) ns_g >>= 1;
+  const size_t crows = (size_t)jl.choice_rows();
+  while (ns_g > 1 && (crows * ns_g * rec * 4 > ((size_t)2 << 30) || crows * ns_g * row * 4 > ((size_t)2 << 30))) ns_g >>= 1;
+  // (chains engine: one chain's shares, as above)
+  if (jl.M_choice > 0 && ((size_t)jl.Mloc * ns_g * rec * 4 > ((size_t)2 << 30) || (size_t)jl.Mloc * ns_g * row * 4 > ((size_t)2 << 30))) return 1;
   const size_t need1 = (size_t)nb * 256 * net.hsum, need2 = (size_t)jl.Mloc * ns_g * rec;
   float* scr = nng_scratch(w, need1 > need2 ? need1 : need2);
   if (!scr) return 1;

@@ -25,7 +25,8 @@ class Engine:
             raise ValueError("pass the handle of a non-default stream (e.g. torch.cuda.Stream().cuda_stream) or None")
         _lib.check(self.lib.dibs_engine_create(C.byref(cfg), C.c_void_p(stream) if stream else None, C.byref(self._h)))
         self.M, self.d, self.k = cfg.n_particles, cfg.n_vars, cfg.n_dim
-        self.B = max(int(cfg.reserved_i[0]), 1)   # problems of a batched engine (include/dibs_hip.h): rows [B * M], problem-major
+        # problems of a batched engine / chains of a chains engine (include/dibs_hip.h): rows [B * M], problem- / chain-major
+        self.B = max(int(cfg.reserved_i[0]), int(cfg.reserved_i[2]), 1)
         self.Mloc = self.B * cfg.n_particles if self.B > 1 else cfg.n_particles // cfg.n_ranks
         self.P = int(self.lib.dibs_engine_theta_size(self._h))
         self.precision = int(self.lib.dibs_engine_precision(self._h))   # 32 or 64: the float64 engine takes and returns double arrays

@@ -58,7 +58,8 @@ typedef struct dibs_config {
   int32_t n_ranks;          /*   [rank*M/n_ranks, (rank+1)*M/n_ranks)                                */
   int32_t device_id;
   int32_t reserved_i[5];    /* [0] n_problems: 0 / 1 = one problem; B > 1 = a batched engine (see dibs_engine_set_data_problem)
-                               [1] precision: 0 / 32 = float32, 64 = the float64 engine (see dibs_engine_set_data_f64) */
+                               [1] precision: 0 / 32 = float32, 64 = the float64 engine (see dibs_engine_set_data_f64)
+                               [2] n_chains: 0 / 1 = one chain (the standalone engine); C > 1 = a chains engine (see CHAINS ENGINE) */
 
   double alpha_linear;      /* dibs.py:70 */
   double beta_linear;       /* dibs.py:71 */
@@ -256,6 +257,23 @@ typedef struct dibs_problem_hparams {
 } dibs_problem_hparams;
 int dibs_engine_set_problem_hparams(dibs_engine* e, int32_t p, const dibs_problem_hparams* hp);
 int dibs_engine_get_problem_hparams(dibs_engine* e, int32_t p, dibs_problem_hparams* hp);
+
+/* CHAINS ENGINE (random restarts of a joint model; the JAX equivalent is vmap of the SVGD loop over keys): dibs_config.reserved_i[2] =
+ * n_chains = C > 1 makes one engine run C independent chains of ONE JointDiBS model (LinearGaussian or DenseNonlinearGaussian, either Z
+ * estimator, any graph prior, either optimizer) on ONE data set: the data, every size and every hyper-parameter are shared, each chain has
+ * its own PRNG key and n_particles = M particles.  Device arrays hold C * M rows, chain-major; each launch of a step covers all chains, the
+ * kernel matrices are block-diagonal [C * M][M] and the SVGD transform sums over a chain's own block.  Chain c ends bit-identical to a
+ * standalone engine run with keys[c] and the same chunking.  It is driven by entry points that exist:
+ *   dibs_engine_set_data(e, x, mask, NULL)              once: the data is shared
+ *   dibs_engine_init_particles_batch(e, keys)           keys: u32 [C][2]; chain c as dibs_engine_init_particles(keys[c])
+ *   dibs_engine_get_keys / dibs_engine_set_keys         the C loop-carry keys, u32 [C][2]
+ *   dibs_engine_get_state / set_state / read_buffer     C * M rows, theta and v_theta included (their key argument must be NULL)
+ *   dibs_engine_run                                     the steps
+ * dibs_engine_create rejects n_chains < 0, n_problems > 1 together with chains, marginal models, n_ranks != 1, float64, n_particles >= 256
+ * per chain (the GEMM form of the SVGD transform is not batched), more than 2^24 rows, and sizes at which a per-row array of C * M rows
+ * (packed rows, scores, partial sums of the acyclicity term, log-probabilities, first-layer tables) would pass 2^31 elements.
+ * dibs_engine_set_data_problem / set_problem_hparams / init_particles, the sharded entry points, step_local* / step_update* / kmat_values,
+ * dibs_engine_eval_gradients and dibs_score_graphs are refused.  Every such failure starts "chains engine (n_chains > 1): ". */
 
 /* FLOAT64 ENGINE (no reference counterpart as such: the reference reaches double precision through JAX_ENABLE_X64,
  * dibs/models/nonlinearGaussian.py:183-185): dibs_config.reserved_i[1] = 64 makes the engine compute what the f64 build of the oracle
