@@ -114,7 +114,7 @@ static int engine_alloc(dibs_engine* e, const dibs_config& c, void* stream) {
     int lo = 0, hi = 0;
     hipDeviceGetStreamPriorityRange(&lo, &hi);  // (lo = least, hi = greatest priority)
     // round 3, headline size: serial 3 906 steps/s; second stream at least / normal / greatest priority 3 906 / 3 964 / 4 001.
-    // round 5 (fork by flag, both chains start together -- see flag_fork in step_local): least priority; with the event fork the three
+    // round 5 (fork by flag, both chains start together -- see the flag fork in plan_step, step_plan.h): least priority; with the event fork the three
     // priorities measure the same now (5 193-5 217), configs 3 / 5 gain 1-2 % at the least priority, config 4 is unchanged.
     const int prio = lo;
     // (an optimisation only: without it every kernel goes to the engine stream)

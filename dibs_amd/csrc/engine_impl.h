@@ -16,6 +16,7 @@
 
 #include "../../include/dibs_hip.h"
 #include "launch.h"
+#include "step_plan.h"
 #include <map>
 #include <mutex>
 #include <rccl/rccl.h>  // declarations only: librccl is bound at run time (dibs_rccl, engine_comm.hip), libdibs_hip.so does not link it
@@ -111,7 +112,6 @@ struct dibs_engine {
   float* x;
   int32_t* mask;
   BgeStats bge;
-  bool kmat_fused;  // this step's latent kernel matrix was computed inside the k_bge_sample launch
   float* soft_ds;  // [Mloc, S, d, d]  BGe reparam estimator: per-sample score-space gradients
   float* soft_tri = nullptr;  // ... beyond 128 variables: the waves' packed triangles (factor | inverse columns) in global scratch
   int soft_blocks = 0;        //     of this many persistent blocks (kernels_bge_soft.h, GLOB)
@@ -157,8 +157,8 @@ struct dibs_engine {
   bool debug_drop_flag = false;        // tests: the next step that would publish the join flag does not (dibs_engine_debug_drop_next_flag)
   float* carry_bak = nullptr;          // [Mloc (2 D + 2 P + 1)] z | v_z | theta | v_theta | baseline at the start of the chunk
   Key2 key_bak;
-  bool kmat_early;  // this step's kernel matrices were launched on the second stream (behind the acyclicity kernel)
-  bool kmat_ext;    // ... or by dibs_engine_kmat_values on a stream of the caller (overlapped exchange)
+  KmatPlace kmat_place = KmatPlace::PhaseB;  // where phase A planned this step's kernel matrices (plan_step, step_plan.h); step_update reads it
+  bool kmat_ext;    // the slab of the next phase B was computed by dibs_engine_kmat_values on a stream of the caller (overlapped exchange)
   double t_ms[DIBS_K_COUNT];
   int64_t t_n[DIBS_K_COUNT];
   std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;
@@ -264,7 +264,7 @@ struct DevBuf {
   hipError_t alloc(size_t n) { return dalloc(&p, n); }
 };
 
-// Fork / join of the second stream by events, as step_batch and step_f64 do it (step_local has its own: flags, the edge kernel's stop event):
+// Fork / join of the second stream by events, as step_batch and step_f64 do it (step_local has its own: ForkKind / JoinKind, step_plan.h):
 //   fork() -- the second stream's chain on s2 -- chain_done() -- the main stream's chain -- join() -- the first reader of the chain's results.
 // Without a second stream s2 is the main stream and the calls do nothing; while per-kernel timing is on, chain_done() joins right away.
 struct EventFork {
@@ -311,7 +311,7 @@ inline RowTarget packed_rows(const dibs_engine* e, float* pack) {
 struct StepKeys {
   const Key2 *theta, *lik, *prior;
 };
-enum { TERMS_LIK = 1, TERMS_PRIOR = 2, TERMS_ALL = 3 };
+// (`terms` of step_local: TERMS_LIK, TERMS_PRIOR, TERMS_ALL -- step_plan.h)
 
 // where phase B reads the rows of ALL particles: packed rows (stride E) or the two planes [values | gradients] of the overlapped protocol
 // (one allocation, [2][M][Ev]: both planes share the row stride, the gradient plane starts M * Ev floats later)

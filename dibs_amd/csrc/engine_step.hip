@@ -101,9 +101,7 @@ static void acyc_power_timed(dibs_engine* e, AcycLaunch al, hipStream_t st) {
   acyc_launch_power(al);
 }
 
-// One kernel-matrix algorithm per global particle count, on every rank and at every launch site: from e->tune.kmat_tiled_min particles the tiled
-// kernel (whose entries do not depend on how the work was cut, kernels_kmat.h), below it the direct one.
-static bool kmat_tiled_on(const dibs_engine* e) { return e->kmat_ns_max > 0 && e->M >= e->tune.kmat_tiled_min; }
+static bool kmat_tiled_on(const dibs_engine* e) { return kmat_tiled_on(e->kmat_ns_max, e->M, e->tune.kmat_tiled_min); }  // (step_plan.h)
 // rows of all M particles at x + m * stride + off (len floats); this engine's slab [Mloc][M] (symmetric when it holds every particle)
 static void kmat_launch_tiled(dibs_engine* e, hipStream_t st, const float* x, size_t stride, size_t off, size_t len, float* kout, float scale, float h,
                               const float* kadd, float* ksum) {
@@ -146,12 +144,12 @@ static void launch_acyc(dibs_engine* e, hipStream_t st, Key2 carry, int Mg, floa
 
 // How the edge-score launch tells the second stream that the scores are there: not at all (stream order, or an event recorded behind it), by
 // the launch's own completion signal (hipExtLaunchKernelGGL stop event), or by a sequence number that k_edge_scores_p's last block publishes
-// (++e->fork_seq -> e->fork_flag; needs edge_one_block).  At most one of the two.
+// (++e->fork_seq -> e->fork_flag; needs edge_one_block).  At most one of the two (ForkKind::StopEvent / FlagFromEdge, step_plan.h).
 struct EdgeFork {
   hipEvent_t stop_ev = nullptr;
   bool publish = false;
 };
-static bool edge_one_block(const dibs_engine* e) { return e->d <= 64 && e->k <= 64 && e->edge_kc >= e->k && e->ldk <= 128; }  // one 16-wave block per particle (k_edge_scores_p)
+static bool edge_one_block(const dibs_engine* e) { return edge_one_block(e->d, e->k, e->edge_kc, e->ldk); }  // (step_plan.h)
 // counters: phase time stamps of the tiled kernel while profiling, else null (a stop event is never given while profiling)
 static void launch_edge_scores(dibs_engine* e, hipStream_t st, float alpha, const EdgeFork& fk, unsigned long long* counters) {
   KTimer tm(e, DIBS_K_EDGE, st);
@@ -193,23 +191,21 @@ struct KmatRows {
   size_t stride, off;
 };
 static size_t kmat_lds_bytes(size_t len) { return (size_t)(((len < KMAT_CH ? len : (size_t)KMAT_CH) + 3) & ~(size_t)3) * 4; }
-// This engine's kernel-matrix slab(s) on `st`: the latent one (latent = false: it was computed inside the k_bge_sample launch), then for the
-// joint models theta's with kz / ksum.
+// This engine's kernel-matrix slab(s) on `st`: the latent one, then for the joint models theta's with kz / ksum.
 // tiled (kernels_kmat.h: partial sums per 32 x 32 tile and chunk, then one finishing block per row) from 128 particles: config 4 597 ->
 // 645 steps/s, config 5 108.5 -> 115, config 3 2290 -> 2328 on the same box (each row is read once per tile instead of once per pair)
-static void launch_kmat(dibs_engine* e, hipStream_t st, const KmatRows& z, const KmatRows& th, bool latent = true) {
+static void launch_kmat(dibs_engine* e, hipStream_t st, const KmatRows& z, const KmatRows& th) {
   const dibs_config& c = e->cfg;
   if (kmat_tiled_on(e)) {
-    if (latent) kmat_launch_tiled(e, st, z.base, z.stride, z.off, (size_t)e->D, e->kz, (float)c.scale_latent, (float)c.h_latent, nullptr, nullptr);
+    kmat_launch_tiled(e, st, z.base, z.stride, z.off, (size_t)e->D, e->kz, (float)c.scale_latent, (float)c.h_latent, nullptr, nullptr);
     if (c.joint) kmat_launch_tiled(e, st, th.base, th.stride, th.off, (size_t)e->P, e->kt, (float)c.scale_theta, (float)c.h_theta, e->kz, e->ksum);
     return;
   }
   const int ksym = e->Mloc == e->M;  // single rank: the slab is the whole (symmetric) matrix
   allow_lds(k_kmat, kmat_lds_bytes(e->D > e->P ? e->D : e->P));
   const dim3 kg(e->Mloc, (e->M + KMAT_BT - 1) / KMAT_BT);
-  if (latent)
-    hipLaunchKernelGGL(k_kmat, kg, dim3(256), kmat_lds_bytes(e->D), st, z.base, z.stride, z.off, (int)e->D, e->kz, e->m0, e->M,
-                       (float)c.scale_latent, (float)c.h_latent, ksym, (const float*)nullptr, (float*)nullptr);
+  hipLaunchKernelGGL(k_kmat, kg, dim3(256), kmat_lds_bytes(e->D), st, z.base, z.stride, z.off, (int)e->D, e->kz, e->m0, e->M,
+                     (float)c.scale_latent, (float)c.h_latent, ksym, (const float*)nullptr, (float*)nullptr);
   if (c.joint)
     hipLaunchKernelGGL(k_kmat, kg, dim3(256), kmat_lds_bytes(e->P), st, th.base, th.stride, th.off, (int)e->P, e->kt, e->m0, e->M,
                        (float)c.scale_theta, (float)c.h_theta, ksym, (const float*)e->kz, e->ksum);
@@ -224,6 +220,43 @@ static JointLaunch joint_launch_args(dibs_engine* e, const RowTarget& rt, int Mg
                      0.f, 0.f, 0.f, e->tune.lin_f32, e->tune.nn_f32};
 }
 
+// The estimators of a joint model (LinearGaussian / DenseNonlinearGaussian) on the main stream: two timed launches per family.  M_choice:
+// JointLaunch::M_choice (0: a standalone engine); msg_pre / msg_post: what surrounds the model's name in the message of a failed scratch
+// allocation; swap_baselines: the updated score-function baselines become the loop's.
+static int launch_joint_estimators(dibs_engine* e, const RowTarget& rt, int Mg, float alpha, Key2 carry_theta, Key2 carry_lik, int M_choice,
+                                   const char* msg_pre, const char* msg_post, bool swap_baselines) {
+  const dibs_config& c = e->cfg;
+  JointLaunch jl = joint_launch_args(e, rt, Mg, alpha);
+  jl.M_choice = M_choice;
+  if (c.likelihood == DIBS_LIK_LINGAUSS) {
+    jl.obs_noise = (float)c.lin_obs_noise;
+    jl.mean_edge = (float)c.lin_mean_edge;
+    jl.sig_edge = (float)c.lin_sig_edge;
+    {
+      KTimer tm(e, DIBS_K_LIN_THETA);  // ("lin_logprobs": both log-prob launches)
+      if (joint_lin_all_logprobs(&e->jw, jl, carry_theta, carry_lik)) return fail(std::string(msg_pre) + "LinearGaussian" + msg_post);
+    }
+    {
+      KTimer tm(e, DIBS_K_LIN_Z);      // ("lin_grad": the theta and the Z estimator in one launch)
+      if (joint_lin_all_grads(&e->jw, jl, carry_theta, carry_lik)) return fail(std::string(msg_pre) + "LinearGaussian" + msg_post);
+    }
+  } else {  // DIBS_LIK_DENSENN: the callers are joint models, and dibs_engine_create admits these two likelihoods only
+    const NNParams np_ = nn_params(c);
+    {
+      KTimer tm(e, DIBS_K_NN_THETA);
+      if (joint_nn_dispatch(&e->jw, jl, carry_theta, LIN_MODE_THETA, np_, (size_t)e->P))
+        return fail(std::string(msg_pre) + "DenseNonlinearGaussian" + msg_post);
+    }
+    {
+      KTimer tm(e, DIBS_K_NN_Z);
+      if (joint_nn_dispatch(&e->jw, jl, carry_lik, c.grad_estimator_z == 0 ? LIN_MODE_Z_SCORE : LIN_MODE_Z_REPARAM, np_, (size_t)e->P))
+        return fail(std::string(msg_pre) + "DenseNonlinearGaussian" + msg_post);
+    }
+  }
+  if (swap_baselines) std::swap(e->baseline, e->baseline2);
+  return 0;
+}
+
 // what differs between the tail launches of the steps
 struct TailOpts {
   float alpha, beta;
@@ -232,7 +265,8 @@ struct TailOpts {
   float* w_lik;     // W_lik: output (score_lik) or input -- the estimator's, or zeros when only the prior part is wanted
   bool flag_join;   // the kernel polls e->join_flag for e->join_seq itself (tail_join_wait)
   unsigned long long* counters;  // profiling: phase time stamps; null in production
-  bool tile_in_grad;  // the latent kernel matrix as tile units riding in the launch (TailArgs::kt)
+  int ns = 0, cps = 0, nrider = 0;  // ns > 1: the latent kernel matrix as nrider blocks of tile units riding in the launch (TailArgs::kt;
+                                    // the split of KmatPlace::InTail, step_plan.h)
 };
 // one block per particle: (score estimator: softmax weights -> W_lik,) total score-space gradient, back-projection, packed row
 static void launch_tail(dibs_engine* e, const RowTarget& rt, const TailOpts& o) {
@@ -252,26 +286,14 @@ static void launch_tail(dibs_engine* e, const RowTarget& rt, const TailOpts& o) 
               e->w_tot, o.flag_join ? e->join_flag : nullptr, e->join_seq, e->join_err, e->Mloc,
               KmatTile{nullptr, 0, 0, 0, nullptr, 0, 0, 0, 1, 0, 0, 0, 1, 1, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr}};
   size_t lds_g = lds;
-  int nrider = 0;
-  if (o.tile_in_grad) {
-    const int nta = (e->M + KT_T - 1) / KT_T, tiles = kmat_tile_count(nta, nta, 1), nchunk = kmat_nchunk((int)e->D);
-    // (pieces: enough units for the CUs the particles leave free, one round of them -- measured at the headline size, launch time on the
-    //  event timer: no units 20.7 us; 100 units of 2 chunks 21.2; 70 of 3 chunks 25.2; 200 of 1 chunk on 128 blocks 25.8)
-    int ns = (256 - e->Mloc + tiles - 1) / tiles;
-    ns = ns > nchunk ? nchunk : ns;
-    ns = ns > e->kmat_ns_max ? e->kmat_ns_max : ns;
-    const int cps = (nchunk + ns - 1) / ns;
-    ns = (nchunk + cps - 1) / cps;
-    if (ns > 1) {
-      ta.kt = KmatTile{e->z, (size_t)e->D, 0, (int)e->D, e->kpart, 0, e->Mloc, e->M, nchunk, nta, nta, 1, ns, cps, (float)c.scale_latent,
-                       (float)c.h_latent, e->kz, nullptr, nullptr, e->kmat_ctr};
-      nrider = tiles * ns < 256 - e->Mloc ? tiles * ns : 256 - e->Mloc;
-      lds_g = lds > kmat_tile_lds_bytes() ? lds : kmat_tile_lds_bytes();
-      e->kmat_fused = true;
-    }
+  if (o.ns > 1) {
+    const int nta = (e->M + KT_T - 1) / KT_T, nchunk = kmat_nchunk((int)e->D);
+    ta.kt = KmatTile{e->z, (size_t)e->D, 0, (int)e->D, e->kpart, 0, e->Mloc, e->M, nchunk, nta, nta, 1, o.ns, o.cps, (float)c.scale_latent,
+                     (float)c.h_latent, e->kz, nullptr, nullptr, e->kmat_ctr};
+    lds_g = lds > kmat_tile_lds_bytes() ? lds : kmat_tile_lds_bytes();
   }
   allow_lds(k_particle_grad, lds_g);
-  hipLaunchKernelGGL(k_particle_grad, dim3(e->Mloc + nrider), dim3(TAIL_NT), lds_g, e->stream, ta);
+  hipLaunchKernelGGL(k_particle_grad, dim3(e->Mloc + o.nrider), dim3(TAIL_NT), lds_g, e->stream, ta);
   if (e->w_tot) {
     const size_t lb = backproject_big_lds(e->d);
     allow_lds(k_backproject_big, lb);
@@ -339,6 +361,38 @@ static Key2 key_array_as_carry(const Key2* local, int m0) {
   return Key2{(uint32_t)p, (uint32_t)(p >> 32)};
 }
 
+// what plan_step reads of the engine (step_plan.h)
+static StepFacts step_facts(const dibs_engine* e, bool xk, int terms) {
+  const dibs_config& c = e->cfg;
+  StepFacts f;
+  f.joint = c.joint != 0;
+  f.likelihood = c.likelihood;
+  f.estimator = c.grad_estimator_z;
+  f.d = e->d;
+  f.k = e->k;
+  f.M = e->M;
+  f.Mloc = e->Mloc;
+  f.D = e->D;
+  f.S = e->S;
+  f.edge_kc = e->edge_kc;
+  f.ldk = e->ldk;
+  f.stream2 = e->stream2 != nullptr;
+  f.profiling = e->profiling;
+  f.profiling_concurrent = e->profiling_concurrent;
+  f.flags_now = e->flags_now;
+  f.fork_flag = e->fork_flag != nullptr;
+  f.kmat_ns_max = e->kmat_ns_max;
+  f.kmat_ctr = e->kmat_ctr != nullptr;
+  f.w_tot = e->w_tot != nullptr;
+  f.kmat_ext = e->kmat_ext;
+  f.xk = xk;
+  f.terms = terms;
+  f.kmat_tiled_min = e->tune.kmat_tiled_min;
+  f.no_kmat_fuse = e->tune.no_kmat_fuse;
+  f.no_kmat_grad = e->tune.no_kmat_grad;
+  return f;
+}
+
 // xk == null: the step of the SVGD loop (keys from the loop-carry key, which advances).  xk != null: the same kernels with the caller's
 // per-particle keys, the loop-carry key untouched; `terms` selects the likelihood part (estimators + their share of grad_z), the prior
 // part (acyclicity, Gaussian and graph prior), or both.
@@ -365,68 +419,28 @@ int step_local(dibs_engine* e, int t, const RowTarget& rt, const StepKeys* xk, i
     carry = next_carry(e, carry);
     e->key = carry;
   }
-  const bool do_lik = (terms & TERMS_LIK) != 0, do_prior = (terms & TERMS_PRIOR) != 0;
+  // every decision of the step's schedule, before the first launch (step_plan.h has the reasons and the measurements)
+  const StepPlan plan = plan_step(step_facts(e, xk != nullptr, terms));
+  const bool fork = plan.fork != ForkKind::None, flag_fork = plan.fork == ForkKind::FlagFromEdge || plan.fork == ForkKind::FlagFromSample;
+  const bool score_lik = plan.score_lik;
+  e->kmat_place = plan.place;
 
-  e->kmat_early = false;
-  e->kmat_fused = false;
-  // While per-kernel timing is on (set_profiling(1)) the main stream joins right away, so that every duration is a kernel alone on the
-  // GPU -- but the launch still goes to the second stream: with that (high-priority) queue in existence the same kernel takes 104 us
-  // on the main stream and 96 us on its own.
-  // (Until round 4 a small acyclicity launch -- <= 512 blocks: config 2, or a rank of a sharded headline run -- stayed on the main stream: the
-  //  fork / join events cost 6 + 6 us of the critical path, more than such a launch could hide.  With the fork as the edge kernel's completion
-  //  signal and the join polled inside k_particle_grad the second stream pays at every size: config 2 18 460 -> 20 440 steps/s, a rank of
-  //  a 4- / 8-way headline run 101.0 -> 91.4 / 85.8 -> 78.0 us per step.)
-  const bool fork = do_prior && do_lik && e->stream2 != nullptr, join_now = e->profiling && !e->profiling_concurrent;
-  // the join inside k_particle_grad (tail_join_wait, agent-scope loads of a flag word the second stream's last kernel stores) instead of an
-  // event wait in front of it: -7 us per step.  The polling blocks hold their CUs while the second stream still has kernels to place, so
-  // the flag is used only while they cannot fill the machine (<= 128 particles: one block each on half of the CUs) and the engine's flags
-  // are on for this chunk (flags_now: latch_flags).  The wait is bounded (join_err; a chunk that saw a time-out is run again on events:
-  // dibs_engine_run, dibs_engine_run_sharded).  Per-kernel timing always uses the event.
-  const bool flag_join = fork && !join_now && e->flags_now && e->Mloc <= 128;
-  // where this step's kernel matrices come from (single rank): the joint models and many particles put them on the second stream behind the
-  // acyclicity chain (kmat_on_s2, see below); otherwise the latent matrix rides inside k_bge_sample
-  const bool kmat_on_s2 = c.joint || (long)e->M * e->D > 4L * e->S * e->d * e->d;
-  const bool kmat_early_now = fork && !xk && kmat_on_s2 && e->Mloc == e->M && !e->kmat_ext;
-  // marginal models, single rank, 128+ particles: the latent matrix as tile units riding in the k_particle_grad launch (TailArgs::kt)
-  const bool tile_in_grad = !c.joint && !xk && !kmat_early_now && !e->kmat_ext && e->Mloc == e->M && e->kmat_ns_max > 1 && e->kmat_ctr != nullptr &&
-                            e->M >= e->tune.kmat_tiled_min && e->Mloc < 256 && e->w_tot == nullptr && !e->tune.no_kmat_fuse && !e->tune.no_kmat_grad;
-  // fork without an event (marginal models): k_edge_scores_p stores what
-  // the second stream reads (scores, exp(-alpha s)) at agent scope, every block counts itself and the last one publishes a sequence number;
-  // one polling wave (k_wait_flag) heads the second stream's chain.  The completion signal cost the NEXT kernel of the main stream 4.7 us
-  // (edge -> sample gap; 1.0 us between plain launches).  With the two chains starting together the acyclicity stream must not have
-  // priority over the sampling kernel (it took the machine: sampling 130 us, the factorisation then alone for 33): the stream is created
-  // with the LOWEST priority.  bench.py, same box: event fork 5 193-5 217 steps/s; flag fork with greatest / normal / lowest priority
-  // 5 218-5 226 / 5 296 / 5 341; config 2 20 560 -> 22 200.  Joint models keep the event (config 3: 2 345 vs 2 311 with the flag).
-  const bool edge_p = edge_one_block(e);
-  const bool flag_fork = flag_join && !c.joint && !e->profiling && e->fork_flag != nullptr && edge_p;
-  // BGe with the score estimator: the flag is published by the FIRST BLOCK OF k_bge_sample instead (it starts when the edge kernel has ended and
-  // released its plain stores): no agent-scope stores and no counting in the edge kernel
-  const bool fork_pub_in_sample = flag_fork && do_lik && c.likelihood == DIBS_LIK_BGE && c.grad_estimator_z == DIBS_EST_SCORE;
-  // fork without a record packet on the main stream: the event is the edge kernel's own completion signal (hipExtLaunchKernel stop event)
-  const bool ext_fork = fork && !e->profiling;
   EdgeFork ef;
-  if (fork_pub_in_sample) ++e->fork_seq;   // (the edge kernel publishes nothing: k_bge_sample's first block does, below)
-  else if (flag_fork) ef.publish = true;   // (the last block publishes fork_seq: k_wait_flag on the second stream)
-  else if (ext_fork) ef.stop_ev = e->ev_fork;
+  if (plan.fork == ForkKind::FlagFromSample) ++e->fork_seq;        // (the edge kernel publishes nothing: k_bge_sample's first block does, below)
+  else if (plan.fork == ForkKind::FlagFromEdge) ef.publish = true;  // (the last block publishes fork_seq: k_wait_flag on the second stream)
+  else if (plan.fork == ForkKind::StopEvent) ef.stop_ev = e->ev_fork;
   launch_edge_scores(e, e->stream, alpha, ef, e->profiling ? e->counters + 8 : nullptr);
-  bool score_lik = false;
   if (fork) {
     if (flag_fork) {
       hipLaunchKernelGGL(k_wait_flag, dim3(1), dim3(64), 0, e->stream2, (const unsigned int*)e->fork_flag, e->fork_seq, 0u, e->join_err);
     } else {
-      if (!ext_fork) hipEventRecord(e->ev_fork, e->stream);
+      if (plan.fork == ForkKind::Event) hipEventRecord(e->ev_fork, e->stream);
       hipStreamWaitEvent(e->stream2, e->ev_fork, 0);
     }
     launch_acyc(e, e->stream2, carry_prior, Mg, alpha);
   }
-  // Single rank: the kernel matrices need only z (and theta), which are final when the step starts.  For the joint models, and for the
-  // marginal model once the matrix is large against the sampling work (M D > 4 S d^2), they follow the acyclicity kernel on the second
-  // stream, which otherwise idles until the likelihood chain on the main stream is done; the join before k_wtotal covers them.
-  // Measured: config 3 (joint, 128 particles) 1 400 -> 1 453 steps/s, config 4 (1 024 particles) 329 -> 395.  At the headline size the
-  // latent matrix stays inside the k_bge_sample launch (KmatFuse: 8 us of that kernel's 70; on the second stream 3 999 -> 3 902 steps/s,
-  // and ahead of the acyclicity kernel it delays that kernel).
-  if (kmat_early_now) {
-    if (join_now) {  // per-kernel timing: one kernel at a time
+  if (plan.place == KmatPlace::Stream2) {
+    if (plan.join == JoinKind::EventAtOnce) {  // per-kernel timing: one kernel at a time
       hipEventRecord(e->ev_k1, e->stream2);
       hipStreamWaitEvent(e->stream, e->ev_k1, 0);
       hipEventRecord(e->ev_k0, e->stream);
@@ -435,36 +449,30 @@ int step_local(dibs_engine* e, int t, const RowTarget& rt, const StepKeys* xk, i
     KTimer tm(e, DIBS_K_KMAT, e->stream2);
     // (Mloc == M here, so m0 == 0 and the slab is the whole symmetric matrix: the arguments launch_kmat derives are the literal 0 and 1)
     launch_kmat(e, e->stream2, KmatRows{e->z, (size_t)e->D, 0}, KmatRows{e->theta, (size_t)e->P, 0});
-    e->kmat_early = true;
   }
-  if (fork) {
-    if (flag_join) {
+  switch (plan.join) {
+    case JoinKind::None: break;
+    case JoinKind::Flag:
       ++e->join_seq;
       if (e->debug_drop_flag) e->debug_drop_flag = false;  // (dibs_engine_debug_drop_next_flag: this step's flag is never stored)
       else hipLaunchKernelGGL(k_join_flag, dim3(1), dim3(1), 0, e->stream2, e->join_flag, e->join_seq);
-    }
-    else hipEventRecord(e->ev_join, e->stream2);
+      break;
+    case JoinKind::EventAtOnce:
+      hipEventRecord(e->ev_join, e->stream2);
+      hipStreamWaitEvent(e->stream, e->ev_join, 0);
+      break;
+    case JoinKind::Event: hipEventRecord(e->ev_join, e->stream2); break;
   }
-  if (fork && join_now) hipStreamWaitEvent(e->stream, e->ev_join, 0);
-  if (!do_lik) {
+  if (!plan.do_lik) {
     // (prior terms only: no estimator runs, the tail takes a zero likelihood gradient)
-  } else if (c.likelihood == DIBS_LIK_BGE && c.grad_estimator_z == DIBS_EST_REPARAM) {
-    const BgeSoftParams sp{e->bge.R, e->bge.Nj, e->bge.alpha_lambd, e->bge.alpha_mu, e->bge.log_t, e->bge.n_mats};
-    KTimer tm(e, DIBS_K_BGE_NODES);
-    bge_soft_launch(sp, e->scores, carry_lik, e->m0, Mg, e->Mloc, e->d, e->S, alpha, (float)c.tau, L, c.logistic_minval_tiny,
-                    e->soft_ds, e->logprobs_z, e->w_lik, e->stream, e->soft_tri, e->soft_blocks);
-  } else if (c.likelihood == DIBS_LIK_BGE) {
+  } else if (score_lik) {
     const BgeParams bp = e->bge.params();
     {  // (queue counters: zero at creation, reset by k_particle_grad at the end of every step)
       KTimer tm(e, DIBS_K_BGE_NODES);
       KmatFuse kf{nullptr, nullptr, 0, 0, 0, 0.f, 0.f, nullptr, 0u};
-      e->kmat_fused = false;
-      // single rank, vector fits one LDS chunk: the latent kernel matrix rides along (see KmatFuse)
-      if (!tile_in_grad && !kmat_tiled_on(e) && !xk && !e->kmat_early && !e->kmat_ext && e->Mloc == e->M && e->D <= KMAT_CH && (size_t)e->D * 4 + 64 <= 80 * 1024 && !e->tune.no_kmat_fuse) {
+      if (plan.place == KmatPlace::InSample)  // the latent kernel matrix rides along (see KmatFuse)
         kf = KmatFuse{e->z, e->kz, (int)e->D, e->M, (e->d + 3) / 4, (float)c.scale_latent, (float)c.h_latent, nullptr, 0u};
-        e->kmat_fused = true;
-      }
-      if (fork_pub_in_sample) {  // (the edge kernel stored plainly and published nothing: this launch's first block does, see KmatFuse)
+      if (plan.fork == ForkKind::FlagFromSample) {  // (the edge kernel stored plainly and published nothing: this launch's first block does, see KmatFuse)
         kf.pub_flag = e->fork_flag;
         kf.pub_seq = e->fork_seq;
       }
@@ -475,45 +483,26 @@ int step_local(dibs_engine* e, int t, const RowTarget& rt, const StepKeys* xk, i
       KTimer tm(e, DIBS_K_BGE_BIG);
       bge_launch_chol(e->stream, e->node_scores, bp, e->bq, e->d, e->S, e->profiling ? e->counters : nullptr);
     }
-    score_lik = true;  // softmax weights, W_lik and the baseline are part of k_particle_grad below
-  } else if (c.likelihood == DIBS_LIK_LINGAUSS) {
-    JointLaunch jl = joint_launch_args(e, rt, Mg, alpha);
-    jl.obs_noise = (float)c.lin_obs_noise;
-    jl.mean_edge = (float)c.lin_mean_edge;
-    jl.sig_edge = (float)c.lin_sig_edge;
-    {
-      KTimer tm(e, DIBS_K_LIN_THETA);  // ("lin_logprobs": both log-prob launches)
-      if (joint_lin_all_logprobs(&e->jw, jl, carry_theta, carry_lik)) return fail("LinearGaussian: scratch area: hipMalloc failed");
-    }
-    {
-      KTimer tm(e, DIBS_K_LIN_Z);      // ("lin_grad": the theta and the Z estimator in one launch)
-      if (joint_lin_all_grads(&e->jw, jl, carry_theta, carry_lik)) return fail("LinearGaussian: scratch area: hipMalloc failed");
-      if (!xk) std::swap(e->baseline, e->baseline2);  // (explicit-key evaluation: the loop's baselines stay, the updated ones are read from baseline2)
-    }
-  } else if (c.likelihood == DIBS_LIK_DENSENN) {
-    const JointLaunch jl = joint_launch_args(e, rt, Mg, alpha);
-    const NNParams np_ = nn_params(c);
-    {
-      KTimer tm(e, DIBS_K_NN_THETA);
-      if (joint_nn_dispatch(&e->jw, jl, carry_theta, LIN_MODE_THETA, np_, (size_t)e->P)) return fail("DenseNonlinearGaussian: scratch area: hipMalloc failed");
-    }
-    {
-      KTimer tm(e, DIBS_K_NN_Z);
-      if (joint_nn_dispatch(&e->jw, jl, carry_lik, c.grad_estimator_z == 0 ? LIN_MODE_Z_SCORE : LIN_MODE_Z_REPARAM, np_, (size_t)e->P))
-        return fail("DenseNonlinearGaussian: scratch area: hipMalloc failed");
-      if (!xk) std::swap(e->baseline, e->baseline2);  // (explicit-key evaluation: the loop's baselines stay, the updated ones are read from baseline2)
-    }
+    // (softmax weights, W_lik and the baseline are part of k_particle_grad below)
+  } else if (c.likelihood == DIBS_LIK_BGE) {  // the reparam estimator
+    const BgeSoftParams sp{e->bge.R, e->bge.Nj, e->bge.alpha_lambd, e->bge.alpha_mu, e->bge.log_t, e->bge.n_mats};
+    KTimer tm(e, DIBS_K_BGE_NODES);
+    bge_soft_launch(sp, e->scores, carry_lik, e->m0, Mg, e->Mloc, e->d, e->S, alpha, (float)c.tau, L, c.logistic_minval_tiny,
+                    e->soft_ds, e->logprobs_z, e->w_lik, e->stream, e->soft_tri, e->soft_blocks);
+  } else {  // a joint model: LinearGaussian or DenseNonlinearGaussian (dibs_engine_create admits no other likelihood)
+    // (explicit-key evaluation: the loop's baselines stay, the updated ones are read from baseline2)
+    if (launch_joint_estimators(e, rt, Mg, alpha, carry_theta, carry_lik, 0, "", ": scratch area: hipMalloc failed", !xk)) return 1;
   }
-  if (fork) {
-    // (covers the kernel matrices: they precede the end of the second stream's chain.  flag_join: k_particle_grad polls the flag itself)
-    if (!flag_join) hipStreamWaitEvent(e->stream, e->ev_join, 0);
-  } else if (do_prior) {
+  if (plan.join == JoinKind::Event || plan.join == JoinKind::EventAtOnce) {
+    // (covers the kernel matrices: they precede the end of the second stream's chain.  Flag: k_particle_grad polls the flag itself)
+    hipStreamWaitEvent(e->stream, e->ev_join, 0);
+  } else if (!fork && plan.do_prior) {
     // (folding this reduction into k_particle_grad for small grids -- one dependent launch less -- was measured and dropped: the tail
     //  kernel grows by more than the launch it saves: config 2 54.3 -> 55.3 us/step, a rank of an 8-way headline run 91.4 -> 99.2)
     launch_acyc(e, e->stream, carry_prior, Mg, alpha);
   }
-  launch_tail(e, rt, TailOpts{alpha, beta, score_lik, do_prior, do_lik ? e->w_lik : const_cast<float*>(zero_w), flag_join,
-                              e->profiling ? e->counters : nullptr, tile_in_grad});
+  launch_tail(e, rt, TailOpts{alpha, beta, score_lik, plan.do_prior, plan.do_lik ? e->w_lik : const_cast<float*>(zero_w),
+                              plan.join == JoinKind::Flag, e->profiling ? e->counters : nullptr, plan.ns, plan.cps, plan.nrider});
   if (score_lik && !xk) std::swap(e->baseline, e->baseline2);
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(err));
@@ -530,9 +519,13 @@ int step_update(dibs_engine* e, int t, const RowSource& rs, float* vals_send) {
   // values right behind this call and sets the flag again; every other caller -- packed protocol, dibs_engine_run, step_update -- leaves
   // it cleared, so that the next overlapped chunk / gather_particles re-gathers instead of using the stale plane)
   e->vals_fresh = false;
-  if (!kmat_ext && !e->kmat_early && (!e->kmat_fused || c.joint)) {
+  // (whether a slab of the caller's is there is known only now: dibs_engine_kmat_values may run beside phase A, after its plan was made,
+  //  and set_state / init_particles discard the slab)
+  KmatPlace place = e->kmat_place;
+  if (place == KmatPlace::External || place == KmatPlace::PhaseB) place = kmat_ext ? KmatPlace::External : KmatPlace::PhaseB;
+  if (place == KmatPlace::PhaseB) {
     KTimer tm(e, DIBS_K_KMAT);
-    launch_kmat(e, e->stream, KmatRows{pack, rs.stride, rs.z_off}, KmatRows{pack, rs.stride, rs.th_off}, !e->kmat_fused);
+    launch_kmat(e, e->stream, KmatRows{pack, rs.stride, rs.z_off}, KmatRows{pack, rs.stride, rs.th_off});
   }
   {
     KTimer tm(e, DIBS_K_PHI_UPDATE);
@@ -679,7 +672,7 @@ int step_batch(dibs_engine* e, int t) {
   if (ef.join()) return 1;
   const RowTarget rt = packed_rows(e, e->pack);
   if (e->hp_tier) batch_tail(e, rt);
-  else launch_tail(e, rt, TailOpts{alpha, beta, true, true, e->w_lik, false, nullptr, false});
+  else launch_tail(e, rt, TailOpts{alpha, beta, true, true, e->w_lik, false, nullptr});
   std::swap(e->baseline, e->baseline2);
   {
     // SVGD transform + optimizer step: k_phi_update's BATCH instantiation, grid.y = problem, each problem exactly a standalone launch
@@ -722,37 +715,11 @@ int step_chains(dibs_engine* e, int t) {
   }
   if (ef.chain_done()) return 1;
   const RowTarget rt = packed_rows(e, e->pack);
-  JointLaunch jl = joint_launch_args(e, rt, -1, alpha);
-  jl.M_choice = e->M;
-  const char* const scratch = ": scratch area: hipMalloc failed, or the partial sums of all chains pass the gradient kernel's addressing limit";
-  if (c.likelihood == DIBS_LIK_LINGAUSS) {
-    jl.obs_noise = (float)c.lin_obs_noise;
-    jl.mean_edge = (float)c.lin_mean_edge;
-    jl.sig_edge = (float)c.lin_sig_edge;
-    {
-      KTimer tm(e, DIBS_K_LIN_THETA);
-      if (joint_lin_all_logprobs(&e->jw, jl, carry_theta, carry_lik)) return fail(std::string("chains engine (n_chains > 1): LinearGaussian") + scratch);
-    }
-    {
-      KTimer tm(e, DIBS_K_LIN_Z);
-      if (joint_lin_all_grads(&e->jw, jl, carry_theta, carry_lik)) return fail(std::string("chains engine (n_chains > 1): LinearGaussian") + scratch);
-    }
-  } else {
-    const NNParams np_ = nn_params(c);
-    {
-      KTimer tm(e, DIBS_K_NN_THETA);
-      if (joint_nn_dispatch(&e->jw, jl, carry_theta, LIN_MODE_THETA, np_, (size_t)e->P))
-        return fail(std::string("chains engine (n_chains > 1): DenseNonlinearGaussian") + scratch);
-    }
-    {
-      KTimer tm(e, DIBS_K_NN_Z);
-      if (joint_nn_dispatch(&e->jw, jl, carry_lik, c.grad_estimator_z == 0 ? LIN_MODE_Z_SCORE : LIN_MODE_Z_REPARAM, np_, (size_t)e->P))
-        return fail(std::string("chains engine (n_chains > 1): DenseNonlinearGaussian") + scratch);
-    }
-  }
-  std::swap(e->baseline, e->baseline2);
+  if (launch_joint_estimators(e, rt, -1, alpha, carry_theta, carry_lik, e->M, "chains engine (n_chains > 1): ",
+                              ": scratch area: hipMalloc failed, or the partial sums of all chains pass the gradient kernel's addressing limit", true))
+    return 1;
   if (ef.join()) return 1;
-  launch_tail(e, rt, TailOpts{alpha, beta, false, true, e->w_lik, false, nullptr, false});
+  launch_tail(e, rt, TailOpts{alpha, beta, false, true, e->w_lik, false, nullptr});
   {
     KTimer tm(e, DIBS_K_PHI_UPDATE);
     launch_phi_update(e, e->pack, (size_t)e->E, PhiSeg{0, (size_t)e->D, (size_t)e->D, 0, e->z, e->vz, e->phi_z, (float)c.h_latent}, e->M, nullptr, 0);

@@ -1,6 +1,7 @@
 // latent / parameter kernel matrix slab (device function shared by k_kmat and the ride-along blocks of k_bge_sample)
 #pragma once
 #include "common.h"
+#include "kmat_consts.h"  // KT_CH, KT_T, KMAT_CH, kmat_tile_count, kmat_nchunk
 
 // The latent kernel matrix only needs z, which is final when a step starts.  On a single rank its blocks ride along in the
 // k_bge_sample launch (extra blockIdx.x range): that kernel is bound by VALU issue, k_kmat by the latency of the far cache
@@ -36,8 +37,6 @@ struct KmatFuse {
 //     config 5 108.5 -> 115; config 3 2 290 -> 2 330.
 //     reference: kernel.py:20-30 / 52-71, svgd.py:165-176 / 537-551
 // ------------------------------------------------------------------------------------------------
-#define KT_CH 256
-#define KT_T 32
 #define KT_LD (KT_CH + 4)  // row stride (floats): 16-byte aligned, rows 4 banks apart (conflict-free 16-byte reads of 8 different rows)
 struct KmatTile {
   const float* x;        // rows [M][stride], the segment starts at `off`; all rows within 4 GiB of x (32-bit byte offsets)
@@ -75,8 +74,7 @@ __host__ inline bool kmat_tile_addressable(size_t rows, size_t stride, size_t of
   return (rows * stride + off + len) * 4 < ((size_t)1 << 32);
 }
 __host__ __device__ inline size_t kmat_tile_lds_bytes() { return (size_t)2 * KT_T * KT_LD * 4; }  // (>= 16 x 1024 floats of partial sums)
-__host__ __device__ inline int kmat_tile_count(int nta, int ntb, int symmetric) { return symmetric ? nta * (nta + 1) / 2 : nta * ntb; }
-__host__ __device__ inline int kmat_nchunk(int len) { return (len + KT_CH - 1) / KT_CH; }
+// (kmat_tile_count, kmat_nchunk: kmat_consts.h)
 
 // (tile, chunk) units by a block of KT_NT = 1024 threads.  Staging: 64 row pieces as float4 (16-byte aligned rows) or scalars, 16 floats per
 // thread, fetched for the NEXT unit of the block while the current one is computed.  Wave w takes the elements 16 w .. 16 w + 15 of the chunk;
@@ -456,7 +454,6 @@ __device__ __forceinline__ void kmat_finish_row(const double* __restrict__ part,
 //     reference: kernel.py:20-30 / 52-71, svgd.py:165-176 / 537-551
 // grid = Mloc, block = 256; dynamic LDS = len * 4
 // ------------------------------------------------------------------------------------------------
-#define KMAT_CH 32768  // floats of z_a staged in LDS at a time (128 KiB); longer vectors (DenseNN theta at d = 100) go in chunks
 __device__ __forceinline__ void kmat_block(float* __restrict__ smem, const float* __restrict__ pack, size_t pack_stride,
                                            size_t seg_off, int len, float* __restrict__ kout, int m0, int M, float scale, float h,
                                            int symmetric, int a, int bt, const float* __restrict__ kadd = nullptr,
