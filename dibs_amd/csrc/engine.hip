@@ -539,6 +539,7 @@ int batch_hp_commit(dibs_engine* e) {
   for (int p = 0; p < e->B; ++p) tab[(size_t)p] = derive_problem_hp(e, e->hp_host[(size_t)p]);
   HIP_OK(hipMemcpy(e->hp, tab.data(), tab.size() * sizeof(ProblemHP), hipMemcpyHostToDevice));
   e->hp_final = true;
+  std::vector<LinGramHost>().swap(e->cdata.gram);  // (chains engine, per-chain data: the data is final too -- the host copies of the Gram matrices go)
   return 0;
 }
 
@@ -622,6 +623,12 @@ static int run_chunk(dibs_engine* e, int t_start, int n_steps, Step step) {
 extern "C" int dibs_engine_run(dibs_engine* e, int32_t t_start, int32_t n_steps) {
   if (!e) return fail("null engine");
   if (e->B > 1 && !e->chains && !e->has_data) return fail("dibs_engine_set_data_problem has not been called for every problem");
+  if (e->chains && !e->has_data && !e->cdata.set.empty()) {
+    size_t c = 0;
+    while (c < e->cdata.set.size() && e->cdata.set[c]) ++c;
+    return fail("chains engine (n_chains > 1): dibs_engine_run: dibs_engine_set_data_problem has not been called for chain " + std::to_string(c) +
+                " (per-chain data: every chain needs its own)");
+  }
   if (!e->has_data) return fail("dibs_engine_set_data has not been called");
   if (e->chains) {
     HIP_OK(hipSetDevice(e->cfg.device_id));

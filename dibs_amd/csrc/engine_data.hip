@@ -165,6 +165,9 @@ static int bge_prepare(BgeStats* st, const dibs_config& cfg, int d, int N, const
 extern "C" int dibs_engine_set_data(dibs_engine* e, const float* x, const int32_t* interv_mask, const float* bge_mean_obs) {
   if (!e || !x) return fail("null argument");
   if (e->B > 1 && !e->chains) return fail("batched engine: use dibs_engine_set_data_problem");
+  if (e->chains && !e->cdata.set.empty())
+    return fail("chains engine (n_chains > 1): dibs_engine_set_data after dibs_engine_set_data_problem is not supported (the chains of this engine "
+                "have data sets of their own; one shared data set needs a new engine)");
   if (e->f64) {  // float64 engine: the data widened exactly
     const size_t n = (size_t)e->N * e->d;
     std::vector<double> x64(x, x + n), mo64;
@@ -194,13 +197,59 @@ extern "C" int dibs_engine_set_data(dibs_engine* e, const float* x, const int32_
       return fail("LinearGaussian: Gram matrices: hipMalloc failed");
   }
   e->has_data = true;
+  if (e->chains) e->cdata.shared = true;  // (from the first call that succeeded: the chains share this data set)
+  return 0;
+}
+
+// ---- chains engine: data per chain (include/dibs_hip.h, CHAINS ENGINE; JointDiBS + LinearGaussian) ------------------------
+// Chain c's observations and mask go to slice c of the workspace's [C][N][d] arrays (tu_lin.hip, joint_chain_data_*); on the Gram path the
+// chain's matrices are built by the host code of a standalone engine and kept until every chain has arrived, then stacked and uploaded.
+// The engine has its data when every chain has.  Allowed until the particles are initialised (as dibs_engine_set_problem_hparams).
+static int chains_set_data_problem(dibs_engine* e, int32_t c, const float* x, int32_t n_obs, const int32_t* interv_mask,
+                                   const float* bge_mean_obs) {
+  const std::string pre = "chains engine (n_chains > 1): dibs_engine_set_data_problem: ";
+  if (e->cdata.shared)
+    return fail("chains engine (n_chains > 1): dibs_engine_set_data_problem after dibs_engine_set_data is not supported (the chains share the data set "
+                "given by dibs_engine_set_data; per-chain data needs a new engine)");
+  if (e->cfg.likelihood != DIBS_LIK_LINGAUSS)
+    return fail(pre + "per-chain data is LinearGaussian only (DenseNonlinearGaussian chains share one data set: dibs_engine_set_data)");
+  if (!x) return fail(pre + "null argument");
+  if (c < 0 || c >= e->B) return fail(pre + "chain index " + std::to_string(c) + " out of range (n_chains = " + std::to_string(e->B) + ")");
+  if (n_obs != e->N)
+    return fail(pre + "n_obs = " + std::to_string(n_obs) + " but dibs_config.n_observations = " + std::to_string(e->N) +
+                " (the number of observations selects LDS sizes and kernels: every chain has the configuration's)");
+  if (bge_mean_obs) return fail(pre + "bge_mean_obs must be NULL (joint models have no BGe prior mean)");
+  if (e->hp_final)
+    return fail(pre + "called after the particles were initialised (init_particles_batch / set_state / run): give every chain its data first");
+  HIP_OK(hipSetDevice(e->cfg.device_id));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  if (e->stream2) HIP_OK(hipStreamSynchronize(e->stream2));
+  const int C = e->B, d = e->d, N = e->N;
+  const bool gram = !joint_lin_fast_path(d, N, e->tune.lin_gram);  // (d and N only: every chain's choice, and its standalone engine's)
+  e->has_data = false;
+  if (e->cdata.set.empty()) {
+    if (joint_chain_data_alloc(&e->jw, C, e->M, N, d)) return fail(pre + "hipMalloc of the per-chain data [n_chains][n_observations][n_vars] failed");
+    e->cdata.set.assign((size_t)C, 0);
+    if (gram) e->cdata.gram.assign((size_t)C, LinGramHost{});
+  }
+  e->cdata.set[(size_t)c] = 0;
+  if (joint_chain_data_set(&e->jw, c, x, interv_mask, N, d)) return fail(pre + "copying the chain's data to the device failed");
+  if (gram) joint_lin_gram_host(&e->cdata.gram[(size_t)c], x, interv_mask, N, d);
+  e->cdata.set[(size_t)c] = 1;
+  bool all = true;
+  for (char f : e->cdata.set) all = all && f;
+  if (all && gram && joint_chain_gram_commit(&e->jw, d, e->cdata.gram)) {
+    e->cdata.set[(size_t)c] = 0;  // (this chain's call can be repeated)
+    return fail(pre + "LinearGaussian: Gram matrices of all chains: hipMalloc failed");
+  }
+  e->has_data = all;
   return 0;
 }
 
 // ---- batched engine: data per problem (include/dibs_hip.h, n_problems) ----------------------------------------------------
 extern "C" int dibs_engine_set_data_problem(dibs_engine* e, int32_t p, const float* x, int32_t n_obs, const int32_t* interv_mask,
                                             const float* bge_mean_obs) {
-  if (refuse_chains(e, "dibs_engine_set_data_problem (the chains share one data set: dibs_engine_set_data)")) return 1;
+  if (e && e->chains) return chains_set_data_problem(e, p, x, n_obs, interv_mask, bge_mean_obs);
   if (need_batch(e)) return 1;
   if (!x) return fail("null argument");
   if (p < 0 || p >= e->B) return fail("problem index out of range");

@@ -84,9 +84,16 @@ struct dibs_engine {
   Key2* bcarry = nullptr;                             // [B] loop-carry keys, advanced on the device (k_batch_keys)
   Key2 *bkeys_lik = nullptr, *bkeys_prior = nullptr;  // [B * M] this step's per-particle keys
   // chains engine (cfg.reserved_i[2] = n_chains = C > 1): C chains of ONE joint model on ONE data set.  B = C and the rows are laid out as
-  // a batched engine's (chain-major, M = one chain's particles); the data and every hyper-parameter are shared.  See step_chains.
+  // a batched engine's (chain-major, M = one chain's particles); every hyper-parameter is shared, and so is the data ...  See step_chains.
   bool chains = false;
   Key2* bkeys_theta = nullptr;                        // [C * M] this step's keys of the theta estimator (k_chain_keys)
+  // ... or, LinearGaussian only, every chain on a data set of its own (dibs_engine_set_data_problem for every chain; engine_data.hip): the
+  // device copies live in the workspace (JointWork::n_chain_data), here is what the host keeps until every chain has its data
+  struct ChainData {
+    bool shared = false;            // dibs_engine_set_data was called: the chains share that data set
+    std::vector<char> set;          // [C] chain c was given data (empty: dibs_engine_set_data_problem was never called)
+    std::vector<LinGramHost> gram;  // [C] Gram path: the chains' matrices, stacked and uploaded when the last chain arrives; released by batch_hp_commit
+  } cdata;
   // per-problem hyper-parameters (dibs_engine_set_problem_hparams): the host values, and the device table of what the kernels take from
   // them (ProblemHP, common.h), written ONCE by batch_hp_commit when the particles are initialised -- set_problem_hparams is refused from
   // then on.  hp_tier: the step's kernels read the table (n_vars, n_dim <= 64 and what else batch_hp_tier asks); otherwise only the

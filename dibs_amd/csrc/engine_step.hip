@@ -691,6 +691,8 @@ int step_batch(dibs_engine* e, int t) {
 // kernel matrices [C * M][M] (latent -> kz, theta -> kt and kz + kt -> ksum) and the SVGD transform (k_phi_update's JOINT + BATCH forms,
 // grid.y = chain).  Fork / join of the second stream by events only; every choice a standalone engine makes from its particle count is
 // made from M, one chain's (acyc_cpb, the kernel-matrix algorithm, phi's TA / FULL, JointLaunch::M_choice), never from C * M.
+// With per-chain data (LinearGaussian, dibs_engine_set_data_problem for every chain) the step is the same: the launchers of tu_lin.hip take
+// the per-chain forms of the data-reading kernels (tu_lin_chains.hip) when the workspace holds JointWork::n_chain_data data sets.
 static bool chains_kmat_tiled(const dibs_engine* e) {  // (kmat_tiled_on of a standalone engine of M particles)
   return e->M >= e->tune.kmat_tiled_min && kmat_tile_addressable((size_t)2 * e->M, e->E > e->Ev ? e->E : e->Ev, 0, 0);
 }

@@ -4,6 +4,7 @@
 #pragma once
 #include "common.h"
 #include "../../include/dibs_hip.h"
+#include <vector>
 
 enum { LIN_MODE_THETA = 0, LIN_MODE_Z_SCORE = 1, LIN_MODE_Z_REPARAM = 2, LIN_MODE_GIVEN = 3 };
 
@@ -24,8 +25,20 @@ struct GradPlan {
   unsigned int* ctr_next;  // the other pair: zeroed by this launch's plan kernel for the next launch (no memset launch between the steps)
 };
 
+// Per-chain data of a chains engine (include/dibs_hip.h, CHAINS ENGINE: dibs_engine_set_data_problem for every chain; LinearGaussian only):
+// what the per-chain kernels of tu_lin_chains.hip take instead of one data set's pointers.  A block serves one particle row m, so its chain
+// c = m / M is block-uniform and chain c's slice is a scalar offset.
+struct LinChainData {
+  const float* x;        // [C][N][d]
+  const int32_t* mask;   // [C][N][d]
+  const int* any_mask;   // [C] chain c has interventions (the any_mask argument of its standalone engine's launches)
+  const double* gram;    // Gram path: [C][n_gram][d][d] ...
+  const double* ncnt;    // ... and [C][d]
+  int M;                 // one chain's particles
+};
+
 struct JointWork {
-  float* x;        // [N, d] device copy
+  float* x;        // [N, d] device copy  (per-chain data: [C][N][d], and so is mask)
   int32_t* mask;   // [N, d]
   float* wsm;      // [Mloc, S] softmax weights scratch
   float* ln_tab;   // [Mloc, d, d] DenseNN: per-particle first-layer prior table (kernels_nn.h), else null
@@ -35,6 +48,11 @@ struct JointWork {
   double* gram;    // LinearGaussian Gram path (kernels_lin_gram.h): C^(j) [n_gram][d][d], observations not intervened on j
   double* ncnt;    // [d] their count
   int n_gram;      // 1 without interventions, else d; 0: not built
+  // chains engine with per-chain data (joint_chain_data_*): n_chain_data = C (0: one shared data set), chain_rows = one chain's particles;
+  // x, mask are [C][N][d], gram [C][n_gram][d][d], ncnt [C][d] (n_gram = d as soon as ONE chain has interventions: a mask-free chain's
+  // single matrix is repeated d times -- the same doubles in the same order of summation as its standalone engine reads from one copy)
+  int n_chain_data, chain_rows;
+  int* any_mask_c;  // [C] device
   void* nhf_w1s;   // DenseNN, f16 matrix pipe (kernels_nn_f16.h): scaled first-layer weights per column pair (float2) [Mloc][H][d][ceil(d/2)]
   void* nhf_w1p;   // ... and their packed f16 pieces {h pair, m pair} (uint2), same shape
   int* nhf_ew;     // [Mloc] exponent of the per-particle scale
@@ -127,12 +145,39 @@ __attribute__((visibility("hidden"))) bool joint_grad_plan(JointWork* w, size_t 
 // true: x fits the LDS-resident MFMA kernels; false: the Gram-matrix path of kernels_lin_gram.h runs (joint_lin_set_gram builds C)
 bool joint_lin_fast_path(int d, int N, bool force_gram);
 int joint_lin_set_gram(JointWork* w, const float* x, const int32_t* mask, int N, int d);
+// per-chain data (chains engine): the [C][N][d] arrays allocated once, one chain's slice uploaded, and the Gram matrices of all chains
+// (their host copies, as joint_lin_gram_host built them per chain) stacked and uploaded.  Non-zero: hipMalloc / copy failed
+int joint_chain_data_alloc(JointWork* w, int C, int rows_per_chain, int N, int d);
+int joint_chain_data_set(JointWork* w, int c, const float* x, const int32_t* mask, int N, int d);
+struct LinGramHost {  // one data set's Gram matrices on the host (joint_lin_gram_host): C [n_gram][d][d], cnt [d]
+  std::vector<double> C, cnt;
+  int n_gram = 0;
+};
+void joint_lin_gram_host(LinGramHost* g, const float* x, const int32_t* mask, int N, int d);
+int joint_chain_gram_commit(JointWork* w, int d, const std::vector<LinGramHost>& chains);
+LinChainData joint_chain_data(const JointWork& w);
 // (the launchers return non-zero when a scratch area cannot be allocated: nothing was launched from that point on)
 int joint_lin_all_logprobs(JointWork* w, const JointLaunch& jl, Key2 carry_theta, Key2 carry_z);
 int joint_lin_all_grads(JointWork* w, const JointLaunch& jl, Key2 carry_theta, Key2 carry_z);
 // log p(theta_i, D | g_i) of n given (graph, parameter) pairs (held-out scoring; dibs_score_graphs)
 int joint_lin_score_given(const JointWork& jw, const float* theta, const int32_t* g, float* out, int n, int d, int N, float obs_noise,
                           float mean_edge, float sig_edge, hipStream_t stream);
+
+// ---- tu_lin_chains.hip: the per-chain forms of the six LinearGaussian kernel families (LinChainData) -----
+// Launched by tu_lin.hip's launchers in place of the shared-data kernel they chose, with the grid, LDS size and per-block counts they chose
+// (per = samples / pairs per block).  lin_chains_launch_*: nt = ceil(d / 16); epq, four: the instantiation tu_lin.hip picked
+struct LinGradJob;
+void lin_chains_launch_logprobs(int nt, dim3 grid, size_t lds, const LinChainData& cd, const JointLaunch& jl, float* lp, Key2 carry, int mode, int per);
+void lin_chains_launch_pair(int nt, int epq, dim3 grid, size_t lds, const LinChainData& cd, const JointLaunch& jl, float* lp, Key2 carry, int mode,
+                            int per);
+void lin_chains_launch_hf(int epq, bool four, dim3 grid, size_t lds, const LinChainData& cd, const JointLaunch& jl, float* lp, Key2 carry, int mode,
+                          int per);
+void lin_chains_launch_grad(int nt, dim3 grid, size_t lds, const LinChainData& cd, const JointLaunch& jl, const LinGradJob& jt, const LinGradJob& jz,
+                            const GradSplit& gs);
+void ling_chains_launch_logprobs(dim3 grid, size_t lds, const LinChainData& cd, int ng, const JointLaunch& jl, float* lp, Key2 carry, int mode,
+                                 float* ops_glob);
+void ling_chains_launch_grad(dim3 grid, size_t lds, const LinChainData& cd, int ng, const JointLaunch& jl, const LinGradJob& jt, const LinGradJob& jz,
+                             float* ops_glob, const GradSplit& gs);
 
 // ---- tu_nn.hip: JointDiBS + DenseNonlinearGaussian ---------------------------------------------------
 // true: the tuned one-hidden-layer kernels of kernels_nn.h apply; false: the general path of kernels_nn_generic.h runs

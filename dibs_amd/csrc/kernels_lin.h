@@ -6,29 +6,53 @@
 //            :325-391 (Z, score), :488-551 (theta).  Both contractions run on v_mfma_f32_16x16x4_f32 with x, theta and
 //            the per-sample operand resident in LDS.
 #pragma once
-#ifndef DIBS_TU_LIN
-#error "kernels_lin.h: the LinearGaussian kernels are compiled in tu_lin.hip only"
+#if !defined(DIBS_TU_LIN) && !defined(DIBS_TU_LIN_CHAINS)
+#error "kernels_lin.h: the LinearGaussian kernels are compiled in tu_lin.hip, their per-chain forms in tu_lin_chains.hip, and nowhere else"
 #endif
 #include "kernels_joint.h"
 #include "kernels_acyc_bf16.h"
 #include "kernels_acyc_f16.h"
 
+// The data a kernel of this file reads -- x, mask and the flag any_mask -- comes in one of two forms, chosen by the translation unit:
+//   tu_lin.hip          launch arguments: one data set for every block (standalone engines, chains engines on shared data).  The macros
+//                       below then spell out the parameters the kernels always had, and LIN_CHAIN_DATA is empty.
+//   tu_lin_chains.hip   a LinChainData (joint_launch.h): the kernels are named k_..._chains and LIN_CHAIN_DATA(m) derives x, mask and
+//                       any_mask of the chain of particle row m (m / M: block-uniform, scalar loads and a scalar offset).
+// One source text, so that the two forms cannot drift apart, and no wrapper around the shared-data kernels: as __forceinline__ blocks
+// under two __global__s the register allocation of k_lin_logprobs_pair and k_lin_grad changed.
+#ifdef DIBS_TU_LIN_CHAINS
+#define LIN_K(name_) name_##_chains
+#define LIN_DATA_PARAMS LinChainData cd
+#define LIN_ANY_PARAM
+#define LIN_CHAIN_DATA(m_)                                                           \
+  const int chain_ = (m_) / cd.M;                                                    \
+  const float* __restrict__ x = cd.x + (size_t)chain_ * N * d;                       \
+  const int32_t* __restrict__ mask = cd.mask + (size_t)chain_ * N * d;               \
+  const int any_mask = cd.any_mask[chain_];
+#else
+#define LIN_K(name_) name_
+#define LIN_DATA_PARAMS const float* __restrict__ x, const int32_t* __restrict__ mask
+#define LIN_ANY_PARAM , int any_mask
+#define LIN_CHAIN_DATA(m_)
+#endif
+
 // ------------------------------------------------------------------------------------------------
 // log p(theta, D | G_s) for all samples.  grid = (ceil(S / spb), Mloc), block = 256
 // ------------------------------------------------------------------------------------------------
 template <int NT>
-__global__ __launch_bounds__(256) void k_lin_logprobs(const float* __restrict__ x, const int32_t* __restrict__ mask,
+__global__ __launch_bounds__(256) void LIN_K(k_lin_logprobs)(LIN_DATA_PARAMS,
                                                       const float* __restrict__ theta, const float* __restrict__ scores,
                                                       const uint32_t* __restrict__ thr, float* __restrict__ logprobs, Key2 carry,
                                                       int mode, int m0, int M_global, int d, int N, int S, int spb, float alpha,
-                                                      float tau, int layout, int tiny, float obs_noise, float mu, float sig,
-                                                      int any_mask) {
+                                                      float tau, int layout, int tiny, float obs_noise, float mu, float sig
+                                                      LIN_ANY_PARAM) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const LinGeom g = lin_geom(d, N, NT);
   float* X = smem;
   float* WG = X + (size_t)g.np * g.ldx;
   double* red = reinterpret_cast<double*>(smem + ((((size_t)g.np * g.ldx + (size_t)g.kp * g.ldw) + 3) & ~(size_t)3));
   const int m = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  LIN_CHAIN_DATA(m)
   const size_t dd = (size_t)d * d;
   const float* __restrict__ TH = theta + (size_t)m * dd;
   lin_load_common<NT>(X, x, g, tid);
@@ -69,12 +93,12 @@ __host__ __device__ inline size_t lin_lds_bytes_pair(int d, int NT) {
 // their sample-independent factors (theta, logN(theta), exp(-alpha s) or the Bernoulli threshold, LDS offset) in registers
 // for all pairs of the block; EPQ == 0 recomputes them per pair (large d: the registers go to the x fragments instead).
 template <int NT, int EPQ>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NT <= 4 ? 3 : 1, NT <= 4 ? 3 : 2))) void k_lin_logprobs_pair(const float* __restrict__ x, const int32_t* __restrict__ mask,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NT <= 4 ? 3 : 1, NT <= 4 ? 3 : 2))) void LIN_K(k_lin_logprobs_pair)(LIN_DATA_PARAMS,
                                                            const float* __restrict__ theta, const float* __restrict__ scores,
                                                            const uint32_t* __restrict__ thr, float* __restrict__ logprobs, Key2 carry,
                                                            int mode, int m0, int M_global, int d, int N, int S, int ppb, float alpha,
-                                                           float tau, int layout, int tiny, float obs_noise, float mu, float sig,
-                                                           int any_mask) {
+                                                           float tau, int layout, int tiny, float obs_noise, float mu, float sig
+                                                           LIN_ANY_PARAM) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int LDW = lin_ldw2<NT>(), NU = 2, KSMAX = 4 * NT;
   const int kp = (d + 3) & ~3, ksteps = kp >> 2, nrt = (N + 15) >> 4;
@@ -82,6 +106,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NT <= 4 ? 3
   float* WG1 = WG0 + (size_t)kp * LDW;
   double* red = reinterpret_cast<double*>(smem + (((size_t)2 * kp * LDW + 3) & ~(size_t)3));
   const int m = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  LIN_CHAIN_DATA(m)
   const int dd = d * d;
   const float* __restrict__ TH = theta + (size_t)m * dd;
   const uint32_t* __restrict__ thr_m = thr + (size_t)m * dd;
@@ -240,16 +265,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NT <= 4 ? 3
 // per output element.  (Round 3's three-piece bf16 variant of this kernel was retired in round 6: profiles/HISTORY.md.)
 // grid = (ceil(S / 2 / ppb), Mloc), block = 64 NW, dynamic LDS = 2 * AHF_IMG_BYTES + 256
 template <int EPQ, bool FOUR, int NW>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8 ? 4 : 3, NW == 8 ? 4 : 3))) void k_lin_logprobs_hf(
-    const float* __restrict__ x, const int32_t* __restrict__ mask, const float* __restrict__ theta, const float* __restrict__ scores,
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8 ? 4 : 3, NW == 8 ? 4 : 3))) void LIN_K(k_lin_logprobs_hf)(
+    LIN_DATA_PARAMS, const float* __restrict__ theta, const float* __restrict__ scores,
     const uint32_t* __restrict__ thr, float* __restrict__ logprobs, Key2 carry, int mode, int m0, int M_global, int d, int N, int S, int ppb,
-    float alpha, float tau, int layout, int tiny, float obs_noise, float mu, float sig, int any_mask) {
+    float alpha, float tau, int layout, int tiny, float obs_noise, float mu, float sig LIN_ANY_PARAM) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   unsigned char* const sb = reinterpret_cast<unsigned char*>(smem);
   double* red = reinterpret_cast<double*>(sb + 2 * AHF_IMG_BYTES);
   constexpr int NU = 8 / NW, NTHR = 64 * NW;
   const int nrt = (N + 15) >> 4;
   const int m = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g4 = lane >> 4, r = lane & 15;
+  LIN_CHAIN_DATA(m)
   const int dd = d * d;
   const float* __restrict__ TH = theta + (size_t)m * dd;
   const uint32_t* __restrict__ thr_m = thr + (size_t)m * dd;
@@ -463,12 +489,12 @@ struct LinGradJob {
   int mode;
 };
 template <int NT>
-__global__ __launch_bounds__(256) void k_lin_grad(const float* __restrict__ x, const int32_t* __restrict__ mask,
+__global__ __launch_bounds__(256) void LIN_K(k_lin_grad)(LIN_DATA_PARAMS,
                                                   const float* __restrict__ theta, const float* __restrict__ scores,
                                                   const uint32_t* __restrict__ thr, LinGradJob job0, LinGradJob job1,
                                                   const float* __restrict__ baseline, int m0, int M_global, int d, int N, int S,
                                                   float alpha, float tau, int layout, int tiny, float obs_noise, float mu, float sig,
-                                                  double sf_baseline, int any_mask, GradSplit gs) {
+                                                  double sf_baseline LIN_ANY_PARAM, GradSplit gs) {
   const LinGradJob job = blockIdx.y ? job1 : job0;  // (grid = (Mloc, 2 estimators, shares); particle = (x + z) mod Mloc: see k_nn_grad)
   const float* __restrict__ logprobs = job.logprobs;
   float* __restrict__ out = job.out;
@@ -484,6 +510,7 @@ __global__ __launch_bounds__(256) void k_lin_grad(const float* __restrict__ x, c
   float* RS = WG + (size_t)g.kp * g.ldw;  // residuals [np][ldw]
   double* red = reinterpret_cast<double*>(smem + ((((size_t)g.np * g.ldx + (size_t)g.kp * g.ldw + (size_t)g.np * g.ldw) + 3) & ~(size_t)3));
   const int m = (int)((blockIdx.x + blockIdx.z) % gridDim.x), tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  LIN_CHAIN_DATA(m)
   const size_t dd = (size_t)d * d;
   const float* __restrict__ TH = theta + (size_t)m * dd;
   const Key2 key = lin_mode_key(mode, carry, M_global, m0 + m, layout);

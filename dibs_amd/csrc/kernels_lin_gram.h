@@ -7,10 +7,24 @@
 // quadratic form cancels (terms ~ N var(x), result ~ N obs_noise): it is evaluated in double on the vector ALU.  Cost per sample:
 // d^3 FMA for soft graphs, sum_j l_j d for hard ones -- independent of N.
 #pragma once
-#ifndef DIBS_TU_LIN
-#error "kernels_lin_gram.h defines kernels that are not templates: it is compiled in tu_lin.hip only"
+#if !defined(DIBS_TU_LIN) && !defined(DIBS_TU_LIN_CHAINS)
+#error "kernels_lin_gram.h defines kernels that are not templates: it is compiled in tu_lin.hip and, under the names k_..._chains, in tu_lin_chains.hip only"
 #endif
-#include "kernels_lin.h"  // (LinGradJob)
+#include "kernels_lin.h"  // (LinGradJob, LIN_K)
+
+// the two forms of the data operands (see kernels_lin.h): the Gram matrices and counts as launch arguments, or chain (m / M)'s slices of
+// the stacked arrays [C][n_gram][d][d] and [C][d] (n_gram == -1: one matrix per chain, read through the caches)
+#ifdef DIBS_TU_LIN_CHAINS
+#define LING_DATA_PARAMS LinChainData cd
+#define LING_CNT_PARAM
+#define LING_CHAIN_DATA(m_)                                                                                                  \
+  const double* __restrict__ gram = cd.gram + (size_t)((m_) / cd.M) * (size_t)(n_gram > 1 ? n_gram : 1) * d * d;            \
+  [[maybe_unused]] const double* __restrict__ ncnt = cd.ncnt + (size_t)((m_) / cd.M) * d;
+#else
+#define LING_DATA_PARAMS const double* __restrict__ gram
+#define LING_CNT_PARAM , const double* __restrict__ ncnt
+#define LING_CHAIN_DATA(m_)
+#endif
 
 // v[a][j] = sum_b C^(j)[a][b] w[b][j] for the pairs this thread owns; calls f(a, j, v, c_aj)
 template <typename F>
@@ -34,7 +48,7 @@ __device__ __forceinline__ void ling_cw(const double* __restrict__ Cs, const dou
 // dynamic LDS = d*d*4 (W) + (n_gram == 1 ? d*d*8 : 0) (C) + 64 (ops_glob: 256, grid.x <= S);  n_gram: 1 = one Gram matrix, LDS-resident; d = one per node (interventions);
 // -1 = one matrix that does not fit LDS beside the operands (d > 100), read through the caches
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_ling_logprobs(const double* __restrict__ gram, const double* __restrict__ ncnt, int n_gram,
+__global__ __launch_bounds__(256) void LIN_K(k_ling_logprobs)(LING_DATA_PARAMS LING_CNT_PARAM, int n_gram,
                                                        const float* __restrict__ theta, const float* __restrict__ scores,
                                                        const uint32_t* __restrict__ thr, float* __restrict__ logprobs, Key2 carry, int mode,
                                                        int m0, int M_global, int d, int S, float alpha, float tau, int layout, int tiny,
@@ -48,6 +62,7 @@ __global__ __launch_bounds__(256) void k_ling_logprobs(const double* __restrict_
   double* red = ops_glob ? reinterpret_cast<double*>(smem_raw)
                          : reinterpret_cast<double*>(smem_raw + (n_gram == 1 ? dd * 8 : 0) + ((dd * 4 + 15) & ~(size_t)15));
   const int m = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  LING_CHAIN_DATA(m)
   const float* TH = theta + (size_t)m * dd;
   const Key2 key = (mode == LIN_MODE_GIVEN) ? Key2{0, 0} : lin_mode_key(mode, carry, M_global, m0 + m, layout);
   const uint64_t nbits = (uint64_t)S * dd;
@@ -89,7 +104,7 @@ __global__ __launch_bounds__(256) void k_ling_logprobs(const double* __restrict_
 // (x + z) mod Mloc.  Accumulation goes to a row in global memory -- the output itself while one block does everything, else the block's
 // partial row -- and every element is owned by one thread.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_ling_grad(const double* __restrict__ gram, int n_gram, const float* __restrict__ theta,
+__global__ __launch_bounds__(256) void LIN_K(k_ling_grad)(LING_DATA_PARAMS, int n_gram, const float* __restrict__ theta,
                                                    const float* __restrict__ scores, const uint32_t* __restrict__ thr, LinGradJob job0,
                                                    LinGradJob job1, const float* __restrict__ baseline, int m0, int M_global, int d, int S,
                                                    float alpha, float tau, int layout, int tiny, float obs_noise, float mu, float sig,
@@ -106,6 +121,7 @@ __global__ __launch_bounds__(256) void k_ling_grad(const double* __restrict__ gr
   double* red = ops_glob ? reinterpret_cast<double*>(smem_raw)
                          : reinterpret_cast<double*>(smem_raw + (n_gram == 1 ? dd * 8 : 0) + ((2 * dd * 4 + 15) & ~(size_t)15));
   const int m = (int)((blockIdx.x + blockIdx.z) % gridDim.x), tid = threadIdx.x;
+  LING_CHAIN_DATA(m)
   const float* TH = theta + (size_t)m * dd;
   float* const om_final = job.out + (size_t)m * job.out_stride;
   const Key2 key = lin_mode_key(mode, job.carry, M_global, m0 + m, layout);

@@ -1,10 +1,12 @@
 // translation unit: the joint models' workspace (JointWork: allocation, data, scratch areas) and the JointDiBS + LinearGaussian kernels
-// with their launchers (kernels_lin.h, kernels_lin_gram.h)
+// with their launchers (kernels_lin.h, kernels_lin_gram.h).  The launchers hand a chains engine with per-chain data (JointWork::n_chain_data)
+// to the per-chain kernels of tu_lin_chains.hip, with the launch shape they chose for the shared-data kernel.
 #define DIBS_TU_LIN
 #include "launch.h"
 #include "kernels_lin.h"
 #include "kernels_lin_gram.h"
 #include <stdlib.h>
+#include <string.h>
 #include <vector>
 
 bool joint_lin_fast_path(int d, int N, bool force_gram) {
@@ -13,12 +15,14 @@ bool joint_lin_fast_path(int d, int N, bool force_gram) {
   return !force_gram && d <= 112 && lin_lds_bytes(d, N, (d + 15) / 16, true) <= (size_t)160 * 1024 - 2048;
 }
 
-int joint_lin_set_gram(JointWork* w, const float* x, const int32_t* mask, int N, int d) {
+void joint_lin_gram_host(LinGramHost* g, const float* x, const int32_t* mask, int N, int d) {
   bool any = false;
   if (mask)
     for (size_t i = 0; i < (size_t)N * d; ++i) any |= mask[i] != 0;
   const int ng = any ? d : 1;
-  std::vector<double> C((size_t)ng * d * d, 0.0), cnt(d, 0.0);
+  std::vector<double>&C = g->C, &cnt = g->cnt;
+  C.assign((size_t)ng * d * d, 0.0);
+  cnt.assign(d, 0.0);
   for (int jm = 0; jm < ng; ++jm)
     for (int n = 0; n < N; ++n) {
       if (any && mask[(size_t)n * d + jm]) continue;
@@ -31,6 +35,9 @@ int joint_lin_set_gram(JointWork* w, const float* x, const int32_t* mask, int N,
     }
   for (int j = 0; j < d; ++j)
     for (int n = 0; n < N; ++n) cnt[j] += (any && mask[(size_t)n * d + j]) ? 0.0 : 1.0;
+  g->n_gram = ng;
+}
+static int gram_upload(JointWork* w, const std::vector<double>& C, const std::vector<double>& cnt, int ng) {
   if (w->gram) hipFree(w->gram);
   if (w->ncnt) hipFree(w->ncnt);
   w->gram = nullptr;
@@ -43,6 +50,62 @@ int joint_lin_set_gram(JointWork* w, const float* x, const int32_t* mask, int N,
   w->n_gram = ng;
   return 0;
 }
+int joint_lin_set_gram(JointWork* w, const float* x, const int32_t* mask, int N, int d) {
+  LinGramHost g;
+  joint_lin_gram_host(&g, x, mask, N, d);
+  return gram_upload(w, g.C, g.cnt, g.n_gram);
+}
+// chains engine, per-chain data: every chain's matrices stacked [C][ng][d][d], ng = d as soon as one chain has interventions -- a chain
+// without them then carries its single matrix d times (the doubles its standalone engine reads from one copy, summed in the same order)
+int joint_chain_gram_commit(JointWork* w, int d, const std::vector<LinGramHost>& chains) {
+  int ng = 1;
+  for (const LinGramHost& g : chains) ng = g.n_gram > ng ? g.n_gram : ng;
+  const size_t dd = (size_t)d * d;
+  std::vector<double> C(chains.size() * ng * dd), cnt(chains.size() * (size_t)d);
+  for (size_t c = 0; c < chains.size(); ++c) {
+    const LinGramHost& g = chains[c];
+    for (int j = 0; j < ng; ++j) memcpy(&C[(c * ng + j) * dd], &g.C[(g.n_gram > 1 ? (size_t)j : 0) * dd], dd * 8);
+    memcpy(&cnt[c * d], g.cnt.data(), (size_t)d * 8);
+  }
+  return gram_upload(w, C, cnt, ng);
+}
+int joint_chain_data_alloc(JointWork* w, int C, int rows_per_chain, int N, int d) {
+  const size_t n = (size_t)C * N * d;
+  if (w->x) hipFree(w->x);
+  if (w->mask) hipFree(w->mask);
+  if (w->any_mask_c) hipFree(w->any_mask_c);
+  w->x = nullptr;
+  w->mask = nullptr;
+  w->any_mask_c = nullptr;
+  w->n_chain_data = 0;
+  const bool ok = hipMalloc((void**)&w->x, n * 4) == hipSuccess && hipMalloc((void**)&w->mask, n * 4) == hipSuccess &&
+                  hipMalloc((void**)&w->any_mask_c, (size_t)C * 4) == hipSuccess && hipMemset(w->x, 0, n * 4) == hipSuccess &&
+                  hipMemset(w->mask, 0, n * 4) == hipSuccess && hipMemset(w->any_mask_c, 0, (size_t)C * 4) == hipSuccess;
+  if (!ok) {  // (nothing half-allocated stays behind: the workspace is without data, as before the call)
+    if (w->x) hipFree(w->x);
+    if (w->mask) hipFree(w->mask);
+    if (w->any_mask_c) hipFree(w->any_mask_c);
+    w->x = nullptr;
+    w->mask = nullptr;
+    w->any_mask_c = nullptr;
+    return 1;
+  }
+  w->n_chain_data = C;
+  w->chain_rows = rows_per_chain;
+  w->any_mask = 0;
+  return 0;
+}
+int joint_chain_data_set(JointWork* w, int c, const float* x, const int32_t* mask, int N, int d) {
+  const size_t n = (size_t)N * d;
+  int any = 0;
+  if (mask)
+    for (size_t i = 0; i < n; ++i) any |= mask[i] != 0;
+  if (hipMemcpy(w->x + c * n, x, n * 4, hipMemcpyHostToDevice) != hipSuccess) return 1;
+  if (mask ? hipMemcpy(w->mask + c * n, mask, n * 4, hipMemcpyHostToDevice) != hipSuccess : hipMemset(w->mask + c * n, 0, n * 4) != hipSuccess) return 1;
+  if (hipMemcpy(w->any_mask_c + c, &any, 4, hipMemcpyHostToDevice) != hipSuccess) return 1;
+  return 0;
+}
+LinChainData joint_chain_data(const JointWork& w) { return LinChainData{w.x, w.mask, w.any_mask_c, w.gram, w.ncnt, w.chain_rows}; }
 
 static size_t ling_lds(int d, int n_gram, bool grad) {
   const size_t dd = (size_t)d * d;
@@ -83,6 +146,7 @@ void joint_free(JointWork* w) {
   if (w->nhx_w1p) hipFree(w->nhx_w1p);
   if (w->gram) hipFree(w->gram);
   if (w->ncnt) hipFree(w->ncnt);
+  if (w->any_mask_c) hipFree(w->any_mask_c);
   *w = JointWork{};
 }
 float* joint_gs_scratch(JointWork* w, size_t floats) {
@@ -161,7 +225,7 @@ template <int NT>
 static int joint_lin_logprobs(JointWork* w, const JointLaunch& jl, Key2 carry, int mode) {
   const int spb = 4;
   const size_t lds1 = lin_lds_bytes(jl.d, jl.N, NT, false);
-  allow_lds(k_lin_logprobs<NT>, lds1);
+  if (!w->n_chain_data) allow_lds(k_lin_logprobs<NT>, lds1);  // (per-chain data: lin_chains_launch_* raise the limit of the kernels they launch)
   float* lp = mode == LIN_MODE_THETA ? jl.logprobs_th : jl.logprobs_z;
   const bool paired = jl.layout == 0 && (jl.S & 1) == 0 && (uint64_t)jl.S * jl.d * jl.d < 0xFFFFFFFFull && jl.N <= 128;
   if (paired) {
@@ -176,7 +240,9 @@ static int joint_lin_logprobs(JointWork* w, const JointLaunch& jl, Key2 carry, i
       const int ldsb = 2 * AHF_IMG_BYTES + 256;
       const int epq8 = (jl.d * jl.d + 511) / 512;
 #define LIN_HF_LAUNCH(EPQ_, FOUR_, NW_)                                                                                                      \
-      {                                                                                                                                      \
+      if (w->n_chain_data) {                                                                                                                 \
+        lin_chains_launch_hf(EPQ_, FOUR_, grid, ldsb, joint_chain_data(*w), jl, lp, carry, mode, ppb);                                       \
+      } else {                                                                                                                               \
         allow_lds(k_lin_logprobs_hf<EPQ_, FOUR_, NW_>, ldsb);                                                                                \
         hipLaunchKernelGGL((k_lin_logprobs_hf<EPQ_, FOUR_, NW_>), grid, dim3(64 * NW_), ldsb, jl.stream, w->x, w->mask, jl.theta, jl.scores, \
                            jl.thr, lp, carry, mode, jl.m0, jl.M, jl.d, jl.N, jl.S, ppb, jl.alpha, jl.tau, jl.layout, jl.tiny, jl.obs_noise,  \
@@ -189,7 +255,9 @@ static int joint_lin_logprobs(JointWork* w, const JointLaunch& jl, Key2 carry, i
       return 0;
     }
 #define LIN_PAIR_LAUNCH(EPQ_)                                                                                                      \
-    {                                                                                                                              \
+    if (w->n_chain_data) {                                                                                                         \
+      lin_chains_launch_pair(NT, EPQ_, grid, ldsp, joint_chain_data(*w), jl, lp, carry, mode, ppb);                                \
+    } else {                                                                                                                       \
       allow_lds(k_lin_logprobs_pair<NT, EPQ_>, ldsp);                                                                              \
       hipLaunchKernelGGL((k_lin_logprobs_pair<NT, EPQ_>), grid, dim3(256), ldsp, jl.stream, w->x, w->mask, jl.theta, jl.scores, jl.thr, lp,   \
                          carry, mode, jl.m0, jl.M, jl.d, jl.N, jl.S, ppb, jl.alpha, jl.tau, jl.layout, jl.tiny, jl.obs_noise,         \
@@ -200,6 +268,8 @@ static int joint_lin_logprobs(JointWork* w, const JointLaunch& jl, Key2 carry, i
     else if (NT <= 4) LIN_PAIR_LAUNCH(16)
     else LIN_PAIR_LAUNCH(0)
 #undef LIN_PAIR_LAUNCH
+  } else if (w->n_chain_data) {
+    lin_chains_launch_logprobs(NT, dim3((jl.S + spb - 1) / spb, jl.Mloc), lds1, joint_chain_data(*w), jl, lp, carry, mode, spb);
   } else {
     hipLaunchKernelGGL(k_lin_logprobs<NT>, dim3((jl.S + spb - 1) / spb, jl.Mloc), dim3(256), lds1, jl.stream, w->x, w->mask, jl.theta,
                        jl.scores, jl.thr, lp, carry, mode, jl.m0, jl.M, jl.d, jl.N, jl.S, spb, jl.alpha, jl.tau, jl.layout, jl.tiny,
@@ -211,13 +281,17 @@ static int joint_lin_logprobs(JointWork* w, const JointLaunch& jl, Key2 carry, i
 template <int NT>
 static int joint_lin_grads(JointWork* w, const JointLaunch& jl, Key2 carry_theta, Key2 carry_z) {
   const size_t lds2 = lin_lds_bytes(jl.d, jl.N, NT, true);
-  allow_lds(k_lin_grad<NT>, lds2);
+  if (!w->n_chain_data) allow_lds(k_lin_grad<NT>, lds2);
   const LinGradJob jt{jl.logprobs_th, jl.pack + (size_t)jl.m0 * jl.pack_stride + jl.gtheta_off, jl.pack_stride,
                       jl.copy_theta ? jl.pack + (size_t)jl.m0 * jl.pack_stride + jl.theta_off : nullptr, nullptr, carry_theta, LIN_MODE_THETA};
   const LinGradJob jz{jl.logprobs_z, jl.w_lik, (size_t)jl.d * jl.d, nullptr, jl.baseline_out, carry_z,
                       jl.est_z == 0 ? LIN_MODE_Z_SCORE : LIN_MODE_Z_REPARAM};
   GradSplit gs;
   if (!joint_grad_split(w, (size_t)jl.Mloc * 2, (size_t)((NT + 3) / 4) * NT * 4 * 256, &gs)) return 1;
+  if (w->n_chain_data) {
+    lin_chains_launch_grad(NT, dim3(jl.Mloc, 2, GRAD_NS), lds2, joint_chain_data(*w), jl, jt, jz, gs);
+    return 0;
+  }
   hipLaunchKernelGGL(k_lin_grad<NT>, dim3(jl.Mloc, 2, GRAD_NS), dim3(256), lds2, jl.stream, w->x, w->mask, jl.theta, jl.scores, jl.thr, jt, jz,
                      jl.baseline, jl.m0, jl.M, jl.d, jl.N, jl.S, jl.alpha, jl.tau, jl.layout, jl.tiny, jl.obs_noise, jl.mean_edge,
                      jl.sig_edge, jl.sf_baseline, w->any_mask, gs);
@@ -245,6 +319,12 @@ int joint_lin_all_logprobs(JointWork* w, const JointLaunch& jl, Key2 carry_theta
     const int rows = jl.choice_rows(), gx = glob ? (jl.S < 1024 / rows ? jl.S : (1024 / rows > 1 ? 1024 / rows : 1)) : jl.S;
     float* gs = glob ? joint_gs_scratch(w, (size_t)gx * jl.Mloc * jl.d * jl.d) : nullptr;
     if (glob && !gs) return 1;
+    if (w->n_chain_data) {
+      const LinChainData cd = joint_chain_data(*w);
+      ling_chains_launch_logprobs(dim3(gx, jl.Mloc), lds, cd, ng, jl, jl.logprobs_th, carry_theta, LIN_MODE_THETA, gs);
+      ling_chains_launch_logprobs(dim3(gx, jl.Mloc), lds, cd, ng, jl, jl.logprobs_z, carry_z, mz, gs);
+      return 0;
+    }
     allow_lds(k_ling_logprobs, lds);
     hipLaunchKernelGGL(k_ling_logprobs, dim3(gx, jl.Mloc), dim3(256), lds, jl.stream, w->gram, w->ncnt, ng, jl.theta, jl.scores, jl.thr,
                        jl.logprobs_th, carry_theta, (int)LIN_MODE_THETA, jl.m0, jl.M, jl.d, jl.S, jl.alpha, jl.tau, jl.layout, jl.tiny, jl.obs_noise,
@@ -268,11 +348,15 @@ int joint_lin_all_grads(JointWork* w, const JointLaunch& jl, Key2 carry_theta, K
     if (glob && !gs) return 1;
     GradSplit gsp;
     if (!joint_grad_split(w, (size_t)jl.Mloc * 2, (size_t)jl.d * jl.d, &gsp)) return 1;
-    allow_lds(k_ling_grad, lds);
+    if (!w->n_chain_data) allow_lds(k_ling_grad, lds);
     const LinGradJob jt{jl.logprobs_th, jl.pack + (size_t)jl.m0 * jl.pack_stride + jl.gtheta_off, jl.pack_stride,
                         jl.copy_theta ? jl.pack + (size_t)jl.m0 * jl.pack_stride + jl.theta_off : nullptr, nullptr, carry_theta, LIN_MODE_THETA};
     const LinGradJob jz{jl.logprobs_z, jl.w_lik, (size_t)jl.d * jl.d, nullptr, jl.baseline_out, carry_z,
                         jl.est_z == 0 ? LIN_MODE_Z_SCORE : LIN_MODE_Z_REPARAM};
+    if (w->n_chain_data) {
+      ling_chains_launch_grad(dim3(jl.Mloc, 2, GRAD_NS), lds, joint_chain_data(*w), ng, jl, jt, jz, gs, gsp);
+      return 0;
+    }
     hipLaunchKernelGGL(k_ling_grad, dim3(jl.Mloc, 2, GRAD_NS), dim3(256), lds, jl.stream, w->gram, ng, jl.theta, jl.scores, jl.thr, jt, jz, jl.baseline,
                        jl.m0, jl.M, jl.d, jl.S, jl.alpha, jl.tau, jl.layout, jl.tiny, jl.obs_noise, jl.mean_edge, jl.sig_edge, jl.sf_baseline, gs, gsp);
     return 0;

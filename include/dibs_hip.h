@@ -264,7 +264,8 @@ int dibs_engine_get_problem_hparams(dibs_engine* e, int32_t p, dibs_problem_hpar
  * its own PRNG key and n_particles = M particles.  Device arrays hold C * M rows, chain-major; each launch of a step covers all chains, the
  * kernel matrices are block-diagonal [C * M][M] and the SVGD transform sums over a chain's own block.  Chain c ends bit-identical to a
  * standalone engine run with keys[c] and the same chunking.  It is driven by entry points that exist:
- *   dibs_engine_set_data(e, x, mask, NULL)              once: the data is shared
+ *   dibs_engine_set_data(e, x, mask, NULL)              once: the data is shared;  OR, LinearGaussian only,
+ *   dibs_engine_set_data_problem(e, c, x, n_obs, mask, NULL)   for EVERY chain c: chain c runs on a data set of its own (see below)
  *   dibs_engine_init_particles_batch(e, keys)           keys: u32 [C][2]; chain c as dibs_engine_init_particles(keys[c])
  *   dibs_engine_get_keys / dibs_engine_set_keys         the C loop-carry keys, u32 [C][2]
  *   dibs_engine_get_state / set_state / read_buffer     C * M rows, theta and v_theta included (their key argument must be NULL)
@@ -272,8 +273,20 @@ int dibs_engine_get_problem_hparams(dibs_engine* e, int32_t p, dibs_problem_hpar
  * dibs_engine_create rejects n_chains < 0, n_problems > 1 together with chains, marginal models, n_ranks != 1, float64, n_particles >= 256
  * per chain (the GEMM form of the SVGD transform is not batched), more than 2^24 rows, and sizes at which a per-row array of C * M rows
  * (packed rows, scores, partial sums of the acyclicity term, log-probabilities, first-layer tables) would pass 2^31 elements.
- * dibs_engine_set_data_problem / set_problem_hparams / init_particles, the sharded entry points, step_local* / step_update* / kmat_values,
- * dibs_engine_eval_gradients and dibs_score_graphs are refused.  Every such failure starts "chains engine (n_chains > 1): ". */
+ * dibs_engine_set_problem_hparams / init_particles, the sharded entry points, step_local* / step_update* / kmat_values,
+ * dibs_engine_eval_gradients and dibs_score_graphs are refused.  Every such failure starts "chains engine (n_chains > 1): ".
+ * PER-CHAIN DATA (the evaluation loop of a study: the same model on many data sets of one size; JointDiBS + LinearGaussian).  A chains
+ * engine takes its data in exactly one of the two ways above.  With dibs_engine_set_data_problem the data, the masks and, where x does not
+ * fit LDS, the Gram matrices are stacked per chain ([C][N][d], [C][n_gram][d][d]), and the six LinearGaussian kernel families run in a form
+ * that takes the pointers and the intervention flag of the block's chain (row / M: block-uniform).  Chain c ends bit-identical to a
+ * standalone engine given chain c's data and key -- also where some chains have interventions and others none (there a mask-free chain's
+ * single Gram matrix is repeated n_vars times: the same doubles, summed in the same order).  Rules, each an error that starts
+ * "chains engine (n_chains > 1): " and names the call: dibs_engine_set_data_problem after dibs_engine_set_data and dibs_engine_set_data
+ * after dibs_engine_set_data_problem are refused (a new engine changes the way); a DenseNonlinearGaussian engine refuses it (its chains
+ * share one data set); n_obs must equal dibs_config.n_observations (it selects LDS sizes and kernels), c must be in [0, C), bge_mean_obs
+ * NULL; a chain's data may be given again until the particles are initialised (init_particles_batch / set_state / run), not after -- as
+ * dibs_engine_set_problem_hparams; dibs_engine_run with some but not all chains given data fails and names the first missing chain (with
+ * no data at all: "dibs_engine_set_data has not been called"). */
 
 /* FLOAT64 ENGINE (no reference counterpart as such: the reference reaches double precision through JAX_ENABLE_X64,
  * dibs/models/nonlinearGaussian.py:183-185): dibs_config.reserved_i[1] = 64 makes the engine compute what the f64 build of the oracle
