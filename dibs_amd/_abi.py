@@ -82,6 +82,22 @@ def problem_hparams(cfg):
     return ProblemHparams(**{name: float(getattr(cfg, name)) for name in SWEEPABLE})
 
 
+# the settings a chains engine holds per chain (dibs_chain_hparams, include/dibs_hip.h): SWEEPABLE and the bandwidth of the parameter
+# kernel, in the struct's order (h_theta stands beside h_latent there)
+JOINT_SWEEPABLE = ("alpha_linear", "beta_linear", "h_latent", "h_theta", "stepsize", "score_function_baseline", "latent_prior_std",
+                   "graph_prior_edges_per_node")
+assert sorted(JOINT_SWEEPABLE) == sorted(SWEEPABLE + ("h_theta",))
+
+
+class ChainHparams(C.Structure):
+    _fields_ = [(name, C.c_double) for name in JOINT_SWEEPABLE]
+
+
+def chain_hparams(cfg):
+    """the per-chain settings a dibs_config carries"""
+    return ChainHparams(**{name: float(getattr(cfg, name)) for name in JOINT_SWEEPABLE})
+
+
 def make_config(*, n_vars, n_particles, n_observations, n_dim=None, joint=False, likelihood="bge",
                 graph_prior="er", edges_per_node=2, grad_estimator_z=None, optimizer="rmsprop",
                 stepsize=0.005, alpha_linear=None, beta_linear=1.0, tau=1.0, n_grad_mc_samples=128,

@@ -6,7 +6,7 @@ import ctypes as C
 import os
 import subprocess
 
-from ._abi import DibsConfig, ProblemHparams
+from ._abi import ChainHparams, DibsConfig, ProblemHparams
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("DIBS_HIP_LIB") or os.path.join(_CSRC, "_build", "libdibs_hip.so")  # env: explicit library path
@@ -24,6 +24,7 @@ EXPORTS = [
     "dibs_engine_comm_init_ipc", "dibs_engine_flag_fallbacks", "dibs_engine_debug_drop_next_flag",
     "dibs_engine_set_data_problem", "dibs_engine_init_particles_batch", "dibs_engine_get_keys", "dibs_engine_set_keys",
     "dibs_engine_set_problem_hparams", "dibs_engine_get_problem_hparams",
+    "dibs_engine_set_chain_hparams", "dibs_engine_get_chain_hparams",
     "dibs_engine_set_data_f64", "dibs_engine_set_state_f64", "dibs_engine_get_state_f64", "dibs_engine_precision",
 ]
 
@@ -105,6 +106,8 @@ def load():
     lib.dibs_engine_set_keys.argtypes = [vp, vp]
     lib.dibs_engine_set_problem_hparams.argtypes = [vp, i32, C.POINTER(ProblemHparams)]
     lib.dibs_engine_get_problem_hparams.argtypes = [vp, i32, C.POINTER(ProblemHparams)]
+    lib.dibs_engine_set_chain_hparams.argtypes = [vp, i32, C.POINTER(ChainHparams)]
+    lib.dibs_engine_get_chain_hparams.argtypes = [vp, i32, C.POINTER(ChainHparams)]
     lib.dibs_engine_set_data_f64.argtypes = [vp, vp, vp, vp]
     lib.dibs_engine_set_state_f64.argtypes = [vp] + [vp] * 6
     lib.dibs_engine_get_state_f64.argtypes = [vp] + [vp] * 6

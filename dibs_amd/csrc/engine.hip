@@ -34,6 +34,16 @@ static int64_t theta_size(const dibs_config& c) {
 static bool batch_hp_tier(const dibs_engine* e) {
   return e->B > 1 && !e->chains && e->d <= 64 && e->k <= 64 && e->w_tot == nullptr && e->tune.acyc_pipe != DIBS_PIPE_BF16;
 }
+// ... and a chains engine: the same sizes, for the same reason (dibs_engine_set_chain_hparams); whether a step reads the table is decided
+// when the table is made final (batch_hp_commit: some chain's values differ)
+static bool chains_hp_sizes_ok(const dibs_engine* e) {
+  return e->chains && e->d <= 64 && e->k <= 64 && e->w_tot == nullptr && e->tune.acyc_pipe != DIBS_PIPE_BF16;
+}
+// the configuration's own values: what a problem or chain has until it is given others
+static dibs_chain_hparams config_hparams(const dibs_config& c) {
+  return dibs_chain_hparams{c.alpha_linear, c.beta_linear, c.h_latent, c.h_theta, c.stepsize, c.score_function_baseline, c.latent_prior_std,
+                            c.graph_prior_edges_per_node};
+}
 
 // Engines alive in this process.  The in-kernel flags (fork: k_wait_flag, join: tail_join_wait) are used by an engine that is ALONE in its
 // process -- the production layout, one process per GPU: its two or three streams have a hardware queue each.  Several engines in one process
@@ -198,8 +208,7 @@ static int engine_alloc(dibs_engine* e, const dibs_config& c, void* stream) {
     HIP_OK(dalloc(&e->bkeys_prior, (size_t)e->Mloc));
     if (e->chains) HIP_OK(dalloc(&e->bkeys_theta, (size_t)e->Mloc));
     HIP_OK(dalloc(&e->hp, (size_t)e->B));
-    e->hp_host.assign((size_t)e->B, dibs_problem_hparams{c.alpha_linear, c.beta_linear, c.h_latent, c.stepsize, c.score_function_baseline,
-                                                         c.latent_prior_std, c.graph_prior_edges_per_node});
+    e->hp_host.assign((size_t)e->B, config_hparams(c));
   }
   // (k_phi_gemm reads whole 128-row x 32-column tiles without bounds checks: rows padded to a multiple of 128, one more tile row of slack)
   const size_t kpad = (((Ml + 127) / 128) * 128 - Ml) * e->M + 64;
@@ -244,6 +253,7 @@ static int engine_alloc(dibs_engine* e, const dibs_config& c, void* stream) {
     if (joint_alloc(&e->jw, e->Mloc, e->d, e->N, e->S) != 0) return fail("joint work buffers: hipMalloc failed");
   }
   e->hp_tier = batch_hp_tier(e);
+  e->chain_hp_ok = chains_hp_sizes_ok(e);
   hipDeviceSynchronize();  // the zero fills above ran on the null stream; the engine's own stream does not wait for it
   return 0;
 }
@@ -480,11 +490,12 @@ extern "C" int dibs_engine_set_keys(dibs_engine* e, const uint32_t* keys) {
 }
 
 // ---- batched engine: per-problem hyper-parameters (include/dibs_hip.h, dibs_engine_set_problem_hparams) ---------------------------------
-static dibs_config problem_config(const dibs_engine* e, const dibs_problem_hparams& h) {
+static dibs_config problem_config(const dibs_engine* e, const dibs_chain_hparams& h) {
   dibs_config c = e->cfg;
   c.alpha_linear = h.alpha_linear;
   c.beta_linear = h.beta_linear;
   c.h_latent = h.h_latent;
+  c.h_theta = h.h_theta;
   c.stepsize = h.stepsize;
   c.score_function_baseline = h.score_function_baseline;
   c.latent_prior_std = h.latent_prior_std;
@@ -492,7 +503,7 @@ static dibs_config problem_config(const dibs_engine* e, const dibs_problem_hpara
   return c;
 }
 // the scalars the standalone engine derives on the host from a configuration (launch_tail, launch_phi_update, launch_kmat), per problem
-static ProblemHP derive_problem_hp(const dibs_engine* e, const dibs_problem_hparams& h) {
+static ProblemHP derive_problem_hp(const dibs_engine* e, const dibs_chain_hparams& h) {
   const dibs_config c = problem_config(e, h);
   const float sigz = latent_sigma(c.latent_prior_std, e->k);
   return ProblemHP{c.alpha_linear, c.beta_linear, c.score_function_baseline, 0.f, 0.f, (float)er_log_odds(c), 1.0f / (sigz * sigz),
@@ -500,28 +511,31 @@ static ProblemHP derive_problem_hp(const dibs_engine* e, const dibs_problem_hpar
 }
 static bool same_derived(const ProblemHP& a, const ProblemHP& b) {
   return a.alpha_linear == b.alpha_linear && a.beta_linear == b.beta_linear && a.sf_baseline == b.sf_baseline && a.prior_c == b.prior_c &&
-         a.inv_sig2 == b.inv_sig2 && a.h == b.h && a.stepsize == b.stepsize;
+         a.inv_sig2 == b.inv_sig2 && a.h == b.h && a.stepsize == b.stepsize && a.h_theta == b.h_theta;
 }
 
 extern "C" int dibs_engine_set_problem_hparams(dibs_engine* e, int32_t p, const dibs_problem_hparams* hp) {
   if (!e || !hp) return fail("batched engine: dibs_engine_set_problem_hparams: null engine or argument");
-  if (refuse_chains(e, "dibs_engine_set_problem_hparams (the chains share every hyper-parameter)")) return 1;
+  if (refuse_chains(e, "dibs_engine_set_problem_hparams (the chains of a JointDiBS + LinearGaussian engine take their own values through "
+                       "dibs_engine_set_chain_hparams)"))
+    return 1;
   if (e->B <= 1) return fail("batched engine: dibs_engine_set_problem_hparams needs one (dibs_config.reserved_i[0] = n_problems must be > 1)");
   if (p < 0 || p >= e->B) return fail("batched engine: dibs_engine_set_problem_hparams: problem index out of range");
   if (e->hp_final)
     return fail("batched engine: dibs_engine_set_problem_hparams after the particles were initialised (init_particles_batch / set_state / run): "
                 "latent_prior_std enters the initial draw and the device table is written once");
-  const dibs_config c = problem_config(e, *hp);
+  // (h_theta: a marginal model has no parameter kernel; the configuration's value rides along)
+  const dibs_chain_hparams h{hp->alpha_linear, hp->beta_linear, hp->h_latent, e->cfg.h_theta, hp->stepsize, hp->score_function_baseline,
+                             hp->latent_prior_std, hp->graph_prior_edges_per_node};
+  const dibs_config c = problem_config(e, h);
   if (c.graph_prior == DIBS_PRIOR_ER) {  // (what dibs_engine_create asks of the shared value)
     const double pr = er_edge_prob(c);
     if (!(pr > 0.0 && pr < 1.0)) return fail("batched engine: problem " + std::to_string(p) + ": Erdos-Renyi prior: edge probability must be in (0, 1)");
   }
-  const dibs_problem_hparams cfg_h{e->cfg.alpha_linear, e->cfg.beta_linear, e->cfg.h_latent, e->cfg.stepsize, e->cfg.score_function_baseline,
-                                   e->cfg.latent_prior_std, e->cfg.graph_prior_edges_per_node};
-  if (!e->hp_tier && !same_derived(derive_problem_hp(e, *hp), derive_problem_hp(e, cfg_h)))
+  if (!e->hp_tier && !same_derived(derive_problem_hp(e, h), derive_problem_hp(e, config_hparams(e->cfg))))
     return fail("batched engine: problem " + std::to_string(p) + ": hyper-parameters that differ from the configuration's need n_vars <= 64 and "
                 "n_dim <= 64 (and the default acyclicity pipe); this engine's kernels take them as launch arguments of the whole batch");
-  e->hp_host[(size_t)p] = *hp;
+  e->hp_host[(size_t)p] = h;
   return 0;
 }
 
@@ -529,7 +543,58 @@ extern "C" int dibs_engine_get_problem_hparams(dibs_engine* e, int32_t p, dibs_p
   if (!e || !hp) return fail("batched engine: dibs_engine_get_problem_hparams: null engine or argument");
   if (e->B <= 1) return fail("batched engine: dibs_engine_get_problem_hparams needs one (dibs_config.reserved_i[0] = n_problems must be > 1)");
   if (p < 0 || p >= e->B) return fail("batched engine: dibs_engine_get_problem_hparams: problem index out of range");
-  *hp = e->hp_host[(size_t)p];
+  const dibs_chain_hparams& h = e->hp_host[(size_t)p];
+  *hp = dibs_problem_hparams{h.alpha_linear, h.beta_linear, h.h_latent, h.stepsize, h.score_function_baseline, h.latent_prior_std,
+                             h.graph_prior_edges_per_node};
+  return 0;
+}
+
+// ---- chains engine: per-chain hyper-parameters (include/dibs_hip.h, PER-CHAIN HYPER-PARAMETERS) ------------------------------------------
+static bool differs_from_config(const dibs_engine* e, const dibs_chain_hparams& h) {
+  return !same_derived(derive_problem_hp(e, h), derive_problem_hp(e, config_hparams(e->cfg)));
+}
+bool chains_hp_differ(const dibs_engine* e) {
+  if (!e->chains) return false;
+  for (const dibs_chain_hparams& h : e->hp_host)
+    if (differs_from_config(e, h)) return true;
+  return false;
+}
+
+extern "C" int dibs_engine_set_chain_hparams(dibs_engine* e, int32_t c, const dibs_chain_hparams* hp) {
+  const std::string pre = "chains engine (n_chains > 1): dibs_engine_set_chain_hparams: ";
+  if (!e || !hp) return fail(pre + "null engine or argument");
+  if (!e->chains) return fail(pre + "needs a chains engine (dibs_config.reserved_i[2] = n_chains must be > 1)");
+  if (c < 0 || c >= e->B) return fail(pre + "chain index " + std::to_string(c) + " out of range (n_chains = " + std::to_string(e->B) + ")");
+  if (e->hp_final)
+    return fail(pre + "called after the particles were initialised (init_particles_batch / set_state / run): latent_prior_std enters the "
+                      "initial draw and the device table is written once");
+  const dibs_config cc = problem_config(e, *hp);
+  if (cc.graph_prior == DIBS_PRIOR_ER) {  // (what dibs_engine_create asks of the shared value)
+    const double pr = er_edge_prob(cc);
+    if (!(pr > 0.0 && pr < 1.0)) return fail(pre + "chain " + std::to_string(c) + ": Erdos-Renyi prior: edge probability must be in (0, 1)");
+  }
+  if (differs_from_config(e, *hp)) {
+    if (e->cfg.likelihood != DIBS_LIK_LINGAUSS)
+      return fail(pre + "chain " + std::to_string(c) + ": hyper-parameters that differ from the configuration's are LinearGaussian only (the "
+                        "DenseNonlinearGaussian kernels have no per-chain form: its chains share every hyper-parameter)");
+    if (!e->chain_hp_ok)
+      return fail(pre + "chain " + std::to_string(c) + ": hyper-parameters that differ from the configuration's need n_vars <= 64 and n_dim <= 64 "
+                        "(got " + std::to_string(e->d) + ", " + std::to_string(e->k) + ") and an acyclicity pipe other than bf16; this engine's "
+                        "kernels take them as launch arguments of all chains");
+    if (e->cdata.shared)
+      return fail(pre + "chain " + std::to_string(c) + ": hyper-parameters that differ from the configuration's need per-chain data "
+                        "(dibs_engine_set_data_problem for every chain), but this engine's chains share the data set given by dibs_engine_set_data");
+  }
+  e->hp_host[(size_t)c] = *hp;
+  return 0;
+}
+
+extern "C" int dibs_engine_get_chain_hparams(dibs_engine* e, int32_t c, dibs_chain_hparams* hp) {
+  const std::string pre = "chains engine (n_chains > 1): dibs_engine_get_chain_hparams: ";
+  if (!e || !hp) return fail(pre + "null engine or argument");
+  if (!e->chains) return fail(pre + "needs a chains engine (dibs_config.reserved_i[2] = n_chains must be > 1)");
+  if (c < 0 || c >= e->B) return fail(pre + "chain index " + std::to_string(c) + " out of range (n_chains = " + std::to_string(e->B) + ")");
+  *hp = e->hp_host[(size_t)c];
   return 0;
 }
 
@@ -539,6 +604,12 @@ int batch_hp_commit(dibs_engine* e) {
   for (int p = 0; p < e->B; ++p) tab[(size_t)p] = derive_problem_hp(e, e->hp_host[(size_t)p]);
   HIP_OK(hipMemcpy(e->hp, tab.data(), tab.size() * sizeof(ProblemHP), hipMemcpyHostToDevice));
   e->hp_final = true;
+  if (e->chains) {
+    // the chains' tier: some chain's scalars differ from the configuration's -- step_chains takes the table-reading launches.  The
+    // per-chain forms of the LinearGaussian kernels (per-chain data) read alpha and the baseline rate from the table either way
+    e->hp_tier = chains_hp_differ(e);
+    e->jw.chain_hp = e->hp;
+  }
   std::vector<LinGramHost>().swap(e->cdata.gram);  // (chains engine, per-chain data: the data is final too -- the host copies of the Gram matrices go)
   return 0;
 }
@@ -629,6 +700,9 @@ extern "C" int dibs_engine_run(dibs_engine* e, int32_t t_start, int32_t n_steps)
     return fail("chains engine (n_chains > 1): dibs_engine_run: dibs_engine_set_data_problem has not been called for chain " + std::to_string(c) +
                 " (per-chain data: every chain needs its own)");
   }
+  if (e->chains && e->cdata.set.empty() && chains_hp_differ(e))  // (no data yet, or -- kept out by both setters -- one shared data set)
+    return fail("chains engine (n_chains > 1): dibs_engine_run: some chain's hyper-parameters differ from the configuration's "
+                "(dibs_engine_set_chain_hparams), which needs per-chain data: dibs_engine_set_data_problem has not been called for every chain");
   if (!e->has_data) return fail("dibs_engine_set_data has not been called");
   if (e->chains) {
     HIP_OK(hipSetDevice(e->cfg.device_id));

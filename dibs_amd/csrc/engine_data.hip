@@ -168,6 +168,9 @@ extern "C" int dibs_engine_set_data(dibs_engine* e, const float* x, const int32_
   if (e->chains && !e->cdata.set.empty())
     return fail("chains engine (n_chains > 1): dibs_engine_set_data after dibs_engine_set_data_problem is not supported (the chains of this engine "
                 "have data sets of their own; one shared data set needs a new engine)");
+  if (e->chains && chains_hp_differ(e))
+    return fail("chains engine (n_chains > 1): dibs_engine_set_data: some chain's hyper-parameters differ from the configuration's "
+                "(dibs_engine_set_chain_hparams), which needs per-chain data: dibs_engine_set_data_problem for every chain");
   if (e->f64) {  // float64 engine: the data widened exactly
     const size_t n = (size_t)e->N * e->d;
     std::vector<double> x64(x, x + n), mo64;

@@ -98,9 +98,13 @@ struct dibs_engine {
   // them (ProblemHP, common.h), written ONCE by batch_hp_commit when the particles are initialised -- set_problem_hparams is refused from
   // then on.  hp_tier: the step's kernels read the table (n_vars, n_dim <= 64 and what else batch_hp_tier asks); otherwise only the
   // batch-only kernels do (kernel matrix, phi, keys) and the rest take the configuration's values as launch arguments, as before
-  std::vector<dibs_problem_hparams> hp_host;
+  // Chains engines keep the same host values and the same table per CHAIN (dibs_engine_set_chain_hparams: h_theta as well, which a batched
+  // engine leaves at the configuration's).  chain_hp_ok: the condition of hp_tier for a chains engine, what differing values need;
+  // hp_tier of a chains engine is decided by batch_hp_commit: some chain's derived values differ from the configuration's (step_chains then
+  // takes the table-reading launches, otherwise it is launch for launch what it always was).
+  std::vector<dibs_chain_hparams> hp_host;
   ProblemHP* hp = nullptr;  // [B]
-  bool hp_final = false, hp_tier = false;
+  bool hp_final = false, hp_tier = false, chain_hp_ok = false;
   struct BatchStats {                                 // host copies of the stacked BGe statistics (padded to d matrices per problem)
     std::vector<float> Rp, Qp;
     std::vector<double> gam, Nj, ldR;
@@ -356,6 +360,13 @@ void batch_launch_acyc_power(const AcycLaunch& a, const ProblemHP* hp, int pM);
 void chains_launch_keys(hipStream_t st, Key2* carry, Key2* keys_theta, Key2* keys_lik, Key2* keys_prior, int C, int M, int layout);
 void chains_launch_kmat(hipStream_t st, bool tiled, const float* x, size_t len, float* kout, int C, int M, float scale, float h, const float* kadd,
                         float* ksum, size_t lds_direct);
+// ... and their table-reading forms (per-chain hyper-parameters, dibs_engine::hp_tier of a chains engine): the keys launch also forms this
+// step's alpha and beta of every chain, the kernel matrices take chain p's h (theta_seg: h_theta) from the table
+void chains_launch_keys_hp(hipStream_t st, Key2* carry, Key2* keys_theta, Key2* keys_lik, Key2* keys_prior, int C, int M, int layout, ProblemHP* hp,
+                           int t);
+void chains_launch_kmat_hp(hipStream_t st, bool tiled, const float* x, size_t len, float* kout, int C, int M, float scale, const ProblemHP* hp,
+                           int theta_seg, const float* kadd, float* ksum, size_t lds_direct);
+bool chains_hp_differ(const dibs_engine* e);  // (engine.hip: some chain's host values derive to other scalars than the configuration's)
 // ---- engine_f64.hip ----
 int f64_alloc(dibs_engine* e);
 int f64_init_particles(dibs_engine* e, Key2 isub);

@@ -696,32 +696,66 @@ int step_batch(dibs_engine* e, int t) {
 static bool chains_kmat_tiled(const dibs_engine* e) {  // (kmat_tiled_on of a standalone engine of M particles)
   return e->M >= e->tune.kmat_tiled_min && kmat_tile_addressable((size_t)2 * e->M, e->E > e->Ev ? e->E : e->Ev, 0, 0);
 }
+// Per-chain hyper-parameters (dibs_engine_set_chain_hparams; e->hp_tier of a chains engine: some chain's values differ from the
+// configuration's; LinearGaussian with per-chain data, n_vars, n_dim <= 64): the keys launch also forms every chain's alpha and beta of the
+// step in its row of the table, the edge, acyclicity and tail launches are the table-reading ones of the batched engine with pM = M
+// (batch_edge_scores, batch_acyc; chains_tail below), the kernel matrices take chain p's h / h_theta, phi reads the table as it always did,
+// and the per-chain estimator kernels take alpha and the baseline rate of the block's chain (LinChainData::hp; they always do).  Without
+// differing values the launches below are those of a chains engine on which nothing was set.
+// (the tail of a joint model as launch_tail builds it -- no score-function likelihood, prior terms on, W, U, V in LDS, no riders, no join
+//  flag; alpha, beta, the prior constant, 1 / sigma^2 and the baseline rate: k_particle_grad_batch fills them in from the table)
+static void chains_tail(dibs_engine* e, const RowTarget& rt) {
+  const dibs_config& c = e->cfg;
+  KTimer tm(e, DIBS_K_TAIL);
+  const int ldz = tail_ldz(e->d, e->k, e->S, false, LDS_LIMIT - 2048);
+  const size_t lds = tail_lds_bytes(e->d, ldz, e->S, e->W, false, 0);
+  const TailArgs ta{nullptr, e->masks, e->logprobs_z, e->baseline, e->baseline2, 0.0, nullptr, e->S, e->W, 0, e->probs, e->w_lik,
+                    e->w_acyc, 0.f, 0.f, c.graph_prior, 0.f, e->z, rt.base, rt.stride, rt.copy_vals, 0, e->d, e->k, ldz, 0.f, nullptr, nullptr,
+                    nullptr, 0u, nullptr, e->Mloc,
+                    KmatTile{nullptr, 0, 0, 0, nullptr, 0, 0, 0, 1, 0, 0, 0, 1, 1, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr}};
+  batch_launch_tail(e->stream, ta, e->hp, e->M, e->Mloc, lds);
+}
 int step_chains(dibs_engine* e, int t) {
   const dibs_config& c = e->cfg;
+  const bool tier = e->hp_tier;
   const float alpha = (float)(c.alpha_linear * t), beta = (float)(c.beta_linear * t);
-  chains_launch_keys(e->stream, e->bcarry, e->bkeys_theta, e->bkeys_lik, e->bkeys_prior, e->B, e->M, c.rng_layout);
+  // (per-chain data: the per-chain estimator kernels read the step's alpha from the table, so the keys launch forms it there also when no
+  //  chain's values differ -- the same launch with two more stores per chain)
+  if (tier || e->jw.n_chain_data) chains_launch_keys_hp(e->stream, e->bcarry, e->bkeys_theta, e->bkeys_lik, e->bkeys_prior, e->B, e->M, c.rng_layout, e->hp, t);
+  else chains_launch_keys(e->stream, e->bcarry, e->bkeys_theta, e->bkeys_lik, e->bkeys_prior, e->B, e->M, c.rng_layout);
   const Key2 carry_theta = key_array_as_carry(e->bkeys_theta, 0), carry_lik = key_array_as_carry(e->bkeys_lik, 0),
              carry_prior = key_array_as_carry(e->bkeys_prior, 0);
-  launch_edge_scores(e, e->stream, alpha, EdgeFork{}, nullptr);
+  if (tier) batch_edge_scores(e);
+  else launch_edge_scores(e, e->stream, alpha, EdgeFork{}, nullptr);
   // acyclicity term and both kernel matrices on the second stream (they need only this step's scores / z / theta), the estimators on the first
   const EventFork ef(e);
   if (ef.fork()) return 1;
-  launch_acyc(e, ef.s2, carry_prior, -1, alpha);
+  if (tier) batch_acyc(e, ef.s2, carry_prior);
+  else launch_acyc(e, ef.s2, carry_prior, -1, alpha);
   {
     KTimer tm(e, DIBS_K_KMAT, ef.s2);
     const bool tiled = chains_kmat_tiled(e);
-    chains_launch_kmat(ef.s2, tiled, e->z, (size_t)e->D, e->kz, e->B, e->M, (float)c.scale_latent, (float)c.h_latent, nullptr, nullptr,
-                       kmat_lds_bytes((size_t)e->D));
-    chains_launch_kmat(ef.s2, tiled, e->theta, (size_t)e->P, e->kt, e->B, e->M, (float)c.scale_theta, (float)c.h_theta, e->kz, e->ksum,
-                       kmat_lds_bytes((size_t)e->P));
+    if (tier) {
+      chains_launch_kmat_hp(ef.s2, tiled, e->z, (size_t)e->D, e->kz, e->B, e->M, (float)c.scale_latent, e->hp, 0, nullptr, nullptr,
+                            kmat_lds_bytes((size_t)e->D));
+      chains_launch_kmat_hp(ef.s2, tiled, e->theta, (size_t)e->P, e->kt, e->B, e->M, (float)c.scale_theta, e->hp, 1, e->kz, e->ksum,
+                            kmat_lds_bytes((size_t)e->P));
+    } else {
+      chains_launch_kmat(ef.s2, tiled, e->z, (size_t)e->D, e->kz, e->B, e->M, (float)c.scale_latent, (float)c.h_latent, nullptr, nullptr,
+                         kmat_lds_bytes((size_t)e->D));
+      chains_launch_kmat(ef.s2, tiled, e->theta, (size_t)e->P, e->kt, e->B, e->M, (float)c.scale_theta, (float)c.h_theta, e->kz, e->ksum,
+                         kmat_lds_bytes((size_t)e->P));
+    }
   }
   if (ef.chain_done()) return 1;
   const RowTarget rt = packed_rows(e, e->pack);
+  // (per-chain data: the estimator kernels read alpha and the baseline rate from the table; the two arguments here are not read)
   if (launch_joint_estimators(e, rt, -1, alpha, carry_theta, carry_lik, e->M, "chains engine (n_chains > 1): ",
                               ": scratch area: hipMalloc failed, or the partial sums of all chains pass the gradient kernel's addressing limit", true))
     return 1;
   if (ef.join()) return 1;
-  launch_tail(e, rt, TailOpts{alpha, beta, false, true, e->w_lik, false, nullptr});
+  if (tier) chains_tail(e, rt);
+  else launch_tail(e, rt, TailOpts{alpha, beta, false, true, e->w_lik, false, nullptr});
   {
     KTimer tm(e, DIBS_K_PHI_UPDATE);
     launch_phi_update(e, e->pack, (size_t)e->E, PhiSeg{0, (size_t)e->D, (size_t)e->D, 0, e->z, e->vz, e->phi_z, (float)c.h_latent}, e->M, nullptr, 0);

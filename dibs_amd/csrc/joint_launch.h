@@ -35,6 +35,9 @@ struct LinChainData {
   const double* gram;    // Gram path: [C][n_gram][d][d] ...
   const double* ncnt;    // ... and [C][d]
   int M;                 // one chain's particles
+  // per-chain hyper-parameters (dibs_engine_set_chain_hparams): the engine's device table [C]; the kernels take this step's alpha (written
+  // by the keys launch of the step) and the baseline rate of the block's chain from row c
+  const ProblemHP* hp;
 };
 
 struct JointWork {
@@ -53,6 +56,7 @@ struct JointWork {
   // single matrix is repeated d times -- the same doubles in the same order of summation as its standalone engine reads from one copy)
   int n_chain_data, chain_rows;
   int* any_mask_c;  // [C] device
+  const ProblemHP* chain_hp;  // LinChainData::hp: the engine's per-chain table, set when it is made final (batch_hp_commit)
   void* nhf_w1s;   // DenseNN, f16 matrix pipe (kernels_nn_f16.h): scaled first-layer weights per column pair (float2) [Mloc][H][d][ceil(d/2)]
   void* nhf_w1p;   // ... and their packed f16 pieces {h pair, m pair} (uint2), same shape
   int* nhf_ew;     // [Mloc] exponent of the per-particle scale

@@ -20,20 +20,33 @@
 //                       any_mask of the chain of particle row m (m / M: block-uniform, scalar loads and a scalar offset).
 // One source text, so that the two forms cannot drift apart, and no wrapper around the shared-data kernels: as __forceinline__ blocks
 // under two __global__s the register allocation of k_lin_logprobs_pair and k_lin_grad changed.
+// The annealed alpha of a step and the baseline rate of the score-function estimator follow the data: launch arguments in tu_lin.hip
+// (LIN_ALPHA_PARAM / LIN_SFB_PARAM spell out `float alpha` / `double sf_baseline`), and in tu_lin_chains.hip locals of those names that
+// LIN_CHAIN_DATA / LIN_CHAIN_SFB take from the chain's row of the per-chain table (LinChainData::hp, dibs_engine_set_chain_hparams;
+// block-uniform: scalar loads beside the one of any_mask) -- always: the keys launch of a step writes every chain's alpha there, and the
+// rows of an engine on which nothing was set hold the configuration's values, so the float is the one the chain's standalone engine
+// passes.  The launch arguments of those names are not read (a select between the two cost the gradient kernels scalar registers).
 #ifdef DIBS_TU_LIN_CHAINS
 #define LIN_K(name_) name_##_chains
 #define LIN_DATA_PARAMS LinChainData cd
 #define LIN_ANY_PARAM
+#define LIN_ALPHA_PARAM [[maybe_unused]] float alpha_launch
+#define LIN_SFB_PARAM [[maybe_unused]] double sf_baseline_launch
 #define LIN_CHAIN_DATA(m_)                                                           \
   const int chain_ = (m_) / cd.M;                                                    \
   const float* __restrict__ x = cd.x + (size_t)chain_ * N * d;                       \
   const int32_t* __restrict__ mask = cd.mask + (size_t)chain_ * N * d;               \
-  const int any_mask = cd.any_mask[chain_];
+  const int any_mask = cd.any_mask[chain_];                                          \
+  const float alpha = cd.hp[chain_].alpha;
+#define LIN_CHAIN_SFB const double sf_baseline = cd.hp[chain_].sf_baseline;
 #else
 #define LIN_K(name_) name_
 #define LIN_DATA_PARAMS const float* __restrict__ x, const int32_t* __restrict__ mask
 #define LIN_ANY_PARAM , int any_mask
+#define LIN_ALPHA_PARAM float alpha
+#define LIN_SFB_PARAM double sf_baseline
 #define LIN_CHAIN_DATA(m_)
+#define LIN_CHAIN_SFB
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -43,7 +56,7 @@ template <int NT>
 __global__ __launch_bounds__(256) void LIN_K(k_lin_logprobs)(LIN_DATA_PARAMS,
                                                       const float* __restrict__ theta, const float* __restrict__ scores,
                                                       const uint32_t* __restrict__ thr, float* __restrict__ logprobs, Key2 carry,
-                                                      int mode, int m0, int M_global, int d, int N, int S, int spb, float alpha,
+                                                      int mode, int m0, int M_global, int d, int N, int S, int spb, LIN_ALPHA_PARAM,
                                                       float tau, int layout, int tiny, float obs_noise, float mu, float sig
                                                       LIN_ANY_PARAM) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -96,7 +109,7 @@ template <int NT, int EPQ>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NT <= 4 ? 3 : 1, NT <= 4 ? 3 : 2))) void LIN_K(k_lin_logprobs_pair)(LIN_DATA_PARAMS,
                                                            const float* __restrict__ theta, const float* __restrict__ scores,
                                                            const uint32_t* __restrict__ thr, float* __restrict__ logprobs, Key2 carry,
-                                                           int mode, int m0, int M_global, int d, int N, int S, int ppb, float alpha,
+                                                           int mode, int m0, int M_global, int d, int N, int S, int ppb, LIN_ALPHA_PARAM,
                                                            float tau, int layout, int tiny, float obs_noise, float mu, float sig
                                                            LIN_ANY_PARAM) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -268,7 +281,7 @@ template <int EPQ, bool FOUR, int NW>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8 ? 4 : 3, NW == 8 ? 4 : 3))) void LIN_K(k_lin_logprobs_hf)(
     LIN_DATA_PARAMS, const float* __restrict__ theta, const float* __restrict__ scores,
     const uint32_t* __restrict__ thr, float* __restrict__ logprobs, Key2 carry, int mode, int m0, int M_global, int d, int N, int S, int ppb,
-    float alpha, float tau, int layout, int tiny, float obs_noise, float mu, float sig LIN_ANY_PARAM) {
+    LIN_ALPHA_PARAM, float tau, int layout, int tiny, float obs_noise, float mu, float sig LIN_ANY_PARAM) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   unsigned char* const sb = reinterpret_cast<unsigned char*>(smem);
   double* red = reinterpret_cast<double*>(sb + 2 * AHF_IMG_BYTES);
@@ -493,8 +506,8 @@ __global__ __launch_bounds__(256) void LIN_K(k_lin_grad)(LIN_DATA_PARAMS,
                                                   const float* __restrict__ theta, const float* __restrict__ scores,
                                                   const uint32_t* __restrict__ thr, LinGradJob job0, LinGradJob job1,
                                                   const float* __restrict__ baseline, int m0, int M_global, int d, int N, int S,
-                                                  float alpha, float tau, int layout, int tiny, float obs_noise, float mu, float sig,
-                                                  double sf_baseline LIN_ANY_PARAM, GradSplit gs) {
+                                                  LIN_ALPHA_PARAM, float tau, int layout, int tiny, float obs_noise, float mu, float sig,
+                                                  LIN_SFB_PARAM LIN_ANY_PARAM, GradSplit gs) {
   const LinGradJob job = blockIdx.y ? job1 : job0;  // (grid = (Mloc, 2 estimators, shares); particle = (x + z) mod Mloc: see k_nn_grad)
   const float* __restrict__ logprobs = job.logprobs;
   float* __restrict__ out = job.out;
@@ -511,6 +524,7 @@ __global__ __launch_bounds__(256) void LIN_K(k_lin_grad)(LIN_DATA_PARAMS,
   double* red = reinterpret_cast<double*>(smem + ((((size_t)g.np * g.ldx + (size_t)g.kp * g.ldw + (size_t)g.np * g.ldw) + 3) & ~(size_t)3));
   const int m = (int)((blockIdx.x + blockIdx.z) % gridDim.x), tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   LIN_CHAIN_DATA(m)
+  LIN_CHAIN_SFB
   const size_t dd = (size_t)d * d;
   const float* __restrict__ TH = theta + (size_t)m * dd;
   const Key2 key = lin_mode_key(mode, carry, M_global, m0 + m, layout);

@@ -18,8 +18,10 @@
 #define LING_DATA_PARAMS LinChainData cd
 #define LING_CNT_PARAM
 #define LING_CHAIN_DATA(m_)                                                                                                  \
-  const double* __restrict__ gram = cd.gram + (size_t)((m_) / cd.M) * (size_t)(n_gram > 1 ? n_gram : 1) * d * d;            \
-  [[maybe_unused]] const double* __restrict__ ncnt = cd.ncnt + (size_t)((m_) / cd.M) * d;
+  const int chain_ = (m_) / cd.M;                                                                                            \
+  const double* __restrict__ gram = cd.gram + (size_t)chain_ * (size_t)(n_gram > 1 ? n_gram : 1) * d * d;                   \
+  [[maybe_unused]] const double* __restrict__ ncnt = cd.ncnt + (size_t)chain_ * d;                                          \
+  const float alpha = cd.hp[chain_].alpha;  /* (see kernels_lin.h, LIN_ALPHA_PARAM) */
 #else
 #define LING_DATA_PARAMS const double* __restrict__ gram
 #define LING_CNT_PARAM , const double* __restrict__ ncnt
@@ -51,7 +53,7 @@ __device__ __forceinline__ void ling_cw(const double* __restrict__ Cs, const dou
 __global__ __launch_bounds__(256) void LIN_K(k_ling_logprobs)(LING_DATA_PARAMS LING_CNT_PARAM, int n_gram,
                                                        const float* __restrict__ theta, const float* __restrict__ scores,
                                                        const uint32_t* __restrict__ thr, float* __restrict__ logprobs, Key2 carry, int mode,
-                                                       int m0, int M_global, int d, int S, float alpha, float tau, int layout, int tiny,
+                                                       int m0, int M_global, int d, int S, LIN_ALPHA_PARAM, float tau, int layout, int tiny,
                                                        float obs_noise, float mu, float sig, float* __restrict__ ops_glob) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   double* Cs = reinterpret_cast<double*>(smem_raw);
@@ -107,8 +109,8 @@ __global__ __launch_bounds__(256) void LIN_K(k_ling_logprobs)(LING_DATA_PARAMS L
 __global__ __launch_bounds__(256) void LIN_K(k_ling_grad)(LING_DATA_PARAMS, int n_gram, const float* __restrict__ theta,
                                                    const float* __restrict__ scores, const uint32_t* __restrict__ thr, LinGradJob job0,
                                                    LinGradJob job1, const float* __restrict__ baseline, int m0, int M_global, int d, int S,
-                                                   float alpha, float tau, int layout, int tiny, float obs_noise, float mu, float sig,
-                                                   double sf_baseline, float* __restrict__ ops_glob, GradSplit gs) {
+                                                   LIN_ALPHA_PARAM, float tau, int layout, int tiny, float obs_noise, float mu, float sig,
+                                                   LIN_SFB_PARAM, float* __restrict__ ops_glob, GradSplit gs) {
   const LinGradJob job = blockIdx.y ? job1 : job0;
   const int mode = job.mode;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -122,6 +124,7 @@ __global__ __launch_bounds__(256) void LIN_K(k_ling_grad)(LING_DATA_PARAMS, int 
                          : reinterpret_cast<double*>(smem_raw + (n_gram == 1 ? dd * 8 : 0) + ((2 * dd * 4 + 15) & ~(size_t)15));
   const int m = (int)((blockIdx.x + blockIdx.z) % gridDim.x), tid = threadIdx.x;
   LING_CHAIN_DATA(m)
+  LIN_CHAIN_SFB
   const float* TH = theta + (size_t)m * dd;
   float* const om_final = job.out + (size_t)m * job.out_stride;
   const Key2 key = lin_mode_key(mode, job.carry, M_global, m0 + m, layout);

@@ -1,7 +1,9 @@
 // translation unit: the table-reading kernels of the batched engine (include/dibs_hip.h, dibs_engine_set_problem_hparams; ProblemHP in
 // common.h) and their launchers.  Each is the block of a standalone kernel under a __global__ that takes the scalar(s) of the block's problem
 // from the per-problem table.  A unit of their own, so that the units of the standalone kernels compile what they compiled without them.
-// Further down: the chain-aware kernels of the chains engine (n_chains; keys, block-diagonal kernel matrices) and their launchers.
+// Further down: the chain-aware kernels of the chains engine (n_chains; keys, block-diagonal kernel matrices) and their launchers, each
+// also in a form that reads the per-chain table (dibs_engine_set_chain_hparams); the edge, acyclicity and tail launches above serve a
+// chains engine's table tier as they are, with pM = one chain's particles.
 #define DIBS_TU_BATCH
 #include "engine_impl.h"
 #include "kernels_edge_p.h"
@@ -72,8 +74,9 @@ void batch_launch_acyc_power(const AcycLaunch& a, const ProblemHP* hp, int pM) {
 // per-chain keys of one step from the C device-resident loop-carry keys, in the order of step_local for a joint model (svgd.py:695-703 per
 // chain): carry_theta = carry, carry_lik = row 0 of split(carry_theta, M + 1), carry_prior = row 0 of split(carry_lik, M + 1), and the carry
 // advances to row 0 of split(carry_prior, M + 1); particle m's key of an estimator is row 1 + m of that estimator's split.  grid = C
-__global__ __launch_bounds__(256) void k_chain_keys(Key2* __restrict__ carry, Key2* __restrict__ keys_theta, Key2* __restrict__ keys_lik,
-                                                    Key2* __restrict__ keys_prior, int M, int layout) {
+// (returns carry_prior: thread 0 of the caller advances the carry to row 0 of its split)
+__device__ __forceinline__ Key2 chain_keys_block(Key2* __restrict__ carry, Key2* __restrict__ keys_theta, Key2* __restrict__ keys_lik,
+                                                 Key2* __restrict__ keys_prior, int M, int layout) {
   const int p = blockIdx.x;
   const uint32_t n = (uint32_t)M + 1u;
   const Key2 c_theta = carry[p];
@@ -86,29 +89,62 @@ __global__ __launch_bounds__(256) void k_chain_keys(Key2* __restrict__ carry, Ke
     keys_prior[o] = rng_split_row(c_prior, n, (uint32_t)m + 1u, layout);
   }
   __syncthreads();  // (every thread has read carry[p])
-  if (threadIdx.x == 0) carry[p] = rng_split_row(c_prior, n, 0u, layout);
+  return c_prior;
+}
+__global__ __launch_bounds__(256) void k_chain_keys(Key2* __restrict__ carry, Key2* __restrict__ keys_theta, Key2* __restrict__ keys_lik,
+                                                    Key2* __restrict__ keys_prior, int M, int layout) {
+  const Key2 c_prior = chain_keys_block(carry, keys_theta, keys_lik, keys_prior, M, layout);
+  if (threadIdx.x == 0) carry[blockIdx.x] = rng_split_row(c_prior, (uint32_t)M + 1u, 0u, layout);
+}
+// per-chain hyper-parameters (dibs_engine_set_chain_hparams): the same block, and this step's annealed alpha and beta of chain p to its row
+// of the table -- (float)(alpha_linear * t) with the product in double, as step_local forms it on the host and k_batch_keys for a problem
+__global__ __launch_bounds__(256) void k_chain_keys_hp(Key2* __restrict__ carry, Key2* __restrict__ keys_theta, Key2* __restrict__ keys_lik,
+                                                       Key2* __restrict__ keys_prior, int M, int layout, ProblemHP* __restrict__ hp, int t) {
+  const Key2 c_prior = chain_keys_block(carry, keys_theta, keys_lik, keys_prior, M, layout);
+  if (threadIdx.x == 0) {
+    const int p = blockIdx.x;
+    carry[p] = rng_split_row(c_prior, (uint32_t)M + 1u, 0u, layout);
+    hp[p].alpha = (float)(hp[p].alpha_linear * (double)t);
+    hp[p].beta = (float)(hp[p].beta_linear * (double)t);
+  }
 }
 void chains_launch_keys(hipStream_t st, Key2* carry, Key2* keys_theta, Key2* keys_lik, Key2* keys_prior, int C, int M, int layout) {
   hipLaunchKernelGGL(k_chain_keys, dim3(C), dim3(256), 0, st, carry, keys_theta, keys_lik, keys_prior, M, layout);
+}
+void chains_launch_keys_hp(hipStream_t st, Key2* carry, Key2* keys_theta, Key2* keys_lik, Key2* keys_prior, int C, int M, int layout, ProblemHP* hp,
+                           int t) {
+  hipLaunchKernelGGL(k_chain_keys_hp, dim3(C), dim3(256), 0, st, carry, keys_theta, keys_lik, keys_prior, M, layout, hp, t);
 }
 
 // block-diagonal kernel matrix of one segment (z or theta), kout [C * M][M]: row a of chain p = a / M against the M particles of p only, by
 // the code of the standalone launch (kmat_block, symmetric) -- bit-identical entries; ksum != null: kadd + k as well (the weight matrix
 // kz + kt of the SVGD transform).  grid = (C * M, ceil(M / KMAT_BT))
-__global__ __launch_bounds__(256) void k_kmat_chains(const float* __restrict__ x, size_t stride, int len, float* __restrict__ kout, int M,
-                                                     float scale, float h, const float* __restrict__ kadd, float* __restrict__ ksum) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
+__device__ __forceinline__ void kmat_chains_block(float* smem, const float* __restrict__ x, size_t stride, int len, float* __restrict__ kout, int M,
+                                                  float scale, float h, const float* __restrict__ kadd, float* __restrict__ ksum) {
   const int a = blockIdx.x, p = a / M;
   const size_t ko = (size_t)p * M * M;
   kmat_block(smem, x + (size_t)p * M * stride, stride, 0, len, kout + ko, 0, M, scale, h, 1, a - p * M, blockIdx.y, kadd ? kadd + ko : nullptr,
              ksum ? ksum + ko : nullptr);
 }
+__global__ __launch_bounds__(256) void k_kmat_chains(const float* __restrict__ x, size_t stride, int len, float* __restrict__ kout, int M,
+                                                     float scale, float h, const float* __restrict__ kadd, float* __restrict__ ksum) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  kmat_chains_block(smem, x, stride, len, kout, M, scale, h, kadd, ksum);
+}
+// per-chain hyper-parameters: the bandwidth of the block's chain from the table (theta_seg: the parameter kernel's h_theta)
+__global__ __launch_bounds__(256) void k_kmat_chains_hp(const float* __restrict__ x, size_t stride, int len, float* __restrict__ kout, int M,
+                                                        float scale, const ProblemHP* __restrict__ hp, int theta_seg,
+                                                        const float* __restrict__ kadd, float* __restrict__ ksum) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const ProblemHP& r = hp[blockIdx.x / (unsigned)M];
+  kmat_chains_block(smem, x, stride, len, kout, M, scale, theta_seg ? r.h_theta : r.h, kadd, ksum);
+}
 // ... the tiled form (standalone engines from DibsTuning::kmat_tiled_min particles): blockIdx.y = chain, one piece per tile (nsplit = 1: the
 // entries do not depend on the cut, see KmatTile).  kt describes chain 0
-__global__ __launch_bounds__(KT_NT) void k_kmat_tile_chains(KmatTile kt) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
+__device__ __forceinline__ void kmat_tile_chains_block(float* smem, const KmatTile& kt, float h) {
   const size_t p = blockIdx.y, ko = p * (size_t)kt.M * kt.M;
   KmatTile k = kt;
+  k.h = h;
   k.x = kt.x + p * (size_t)kt.M * kt.stride;
   k.kout = kt.kout + ko;
   if (kt.ksum) {
@@ -116,6 +152,15 @@ __global__ __launch_bounds__(KT_NT) void k_kmat_tile_chains(KmatTile kt) {
     k.ksum = kt.ksum + ko;
   }
   kmat_tile_block(smem, k, (int)blockIdx.x, (int)gridDim.x, (int)threadIdx.x);
+}
+__global__ __launch_bounds__(KT_NT) void k_kmat_tile_chains(KmatTile kt) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  kmat_tile_chains_block(smem, kt, kt.h);
+}
+__global__ __launch_bounds__(KT_NT) void k_kmat_tile_chains_hp(KmatTile kt, const ProblemHP* __restrict__ hp, int theta_seg) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const ProblemHP& r = hp[blockIdx.y];
+  kmat_tile_chains_block(smem, kt, theta_seg ? r.h_theta : r.h);
 }
 // one segment's matrix of every chain on `st`; `tiled`: the choice of a standalone engine of M particles (made by the caller from M alone)
 void chains_launch_kmat(hipStream_t st, bool tiled, const float* x, size_t len, float* kout, int C, int M, float scale, float h, const float* kadd,
@@ -130,4 +175,18 @@ void chains_launch_kmat(hipStream_t st, bool tiled, const float* x, size_t len, 
   dibs_allow_lds((const void*)k_kmat_chains, lds_direct);
   hipLaunchKernelGGL(k_kmat_chains, dim3((unsigned)(C * M), (unsigned)((M + KMAT_BT - 1) / KMAT_BT)), dim3(256), lds_direct, st, x, len, (int)len, kout, M,
                      scale, h, kadd, ksum);
+}
+// ... with chain p's bandwidth from the table (per-chain hyper-parameters): the same grids, LDS sizes and tile descriptions
+void chains_launch_kmat_hp(hipStream_t st, bool tiled, const float* x, size_t len, float* kout, int C, int M, float scale, const ProblemHP* hp,
+                           int theta_seg, const float* kadd, float* ksum, size_t lds_direct) {
+  if (tiled) {
+    const int nta = (M + KT_T - 1) / KT_T, tiles = kmat_tile_count(nta, nta, 1), nchunk = kmat_nchunk((int)len);
+    const KmatTile kt{x, len, 0, (int)len, nullptr, 0, M, M, nchunk, nta, nta, 1, 1, nchunk, scale, 0.f, kout, kadd, ksum, nullptr};
+    dibs_allow_lds((const void*)k_kmat_tile_chains_hp, kmat_tile_lds_bytes());
+    hipLaunchKernelGGL(k_kmat_tile_chains_hp, dim3((unsigned)tiles, (unsigned)C), dim3(KT_NT), kmat_tile_lds_bytes(), st, kt, hp, theta_seg);
+    return;
+  }
+  dibs_allow_lds((const void*)k_kmat_chains_hp, lds_direct);
+  hipLaunchKernelGGL(k_kmat_chains_hp, dim3((unsigned)(C * M), (unsigned)((M + KMAT_BT - 1) / KMAT_BT)), dim3(256), lds_direct, st, x, len, (int)len, kout, M,
+                     scale, hp, theta_seg, kadd, ksum);
 }

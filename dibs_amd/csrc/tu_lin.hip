@@ -105,7 +105,7 @@ int joint_chain_data_set(JointWork* w, int c, const float* x, const int32_t* mas
   if (hipMemcpy(w->any_mask_c + c, &any, 4, hipMemcpyHostToDevice) != hipSuccess) return 1;
   return 0;
 }
-LinChainData joint_chain_data(const JointWork& w) { return LinChainData{w.x, w.mask, w.any_mask_c, w.gram, w.ncnt, w.chain_rows}; }
+LinChainData joint_chain_data(const JointWork& w) { return LinChainData{w.x, w.mask, w.any_mask_c, w.gram, w.ncnt, w.chain_rows, w.chain_hp}; }
 
 static size_t ling_lds(int d, int n_gram, bool grad) {
   const size_t dd = (size_t)d * d;

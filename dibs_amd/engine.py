@@ -3,7 +3,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._abi import BUF, K_COUNT, KERNELS, SWEEPABLE, DibsConfig, ProblemHparams
+from ._abi import BUF, JOINT_SWEEPABLE, K_COUNT, KERNELS, SWEEPABLE, ChainHparams, DibsConfig, ProblemHparams
 
 _BUF_DTYPE = {"NODE_SCORES": np.float64, "PARENT_MASKS": np.uint64}
 # the buffers a float64 engine (include/dibs_hip.h, dibs_config.reserved_i[1] = 64) holds in double
@@ -75,6 +75,21 @@ class Engine:
     def get_problem_hparams(self, p):
         hp = ProblemHparams()
         _lib.check(self.lib.dibs_engine_get_problem_hparams(self._h, int(p), C.byref(hp)))
+        return hp
+
+    def set_chain_hparams(self, c, hparams=None, **kw):
+        """Per-chain hyper-parameters of a chains engine (include/dibs_hip.h, dibs_engine_set_chain_hparams): a ChainHparams, or keywords
+        out of ``_abi.JOINT_SWEEPABLE`` on top of the chain's current values.  Only before the particles are initialised."""
+        hp = self.get_chain_hparams(c) if hparams is None else hparams
+        for name, v in kw.items():
+            if name not in JOINT_SWEEPABLE:
+                raise TypeError(f"{name} is not a per-chain setting (one of {', '.join(JOINT_SWEEPABLE)})")
+            setattr(hp, name, float(v))
+        _lib.check(self.lib.dibs_engine_set_chain_hparams(self._h, int(c), C.byref(hp)))
+
+    def get_chain_hparams(self, c):
+        hp = ChainHparams()
+        _lib.check(self.lib.dibs_engine_get_chain_hparams(self._h, int(c), C.byref(hp)))
         return hp
 
     def init_particles_batch(self, keys):

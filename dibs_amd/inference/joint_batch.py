@@ -13,23 +13,23 @@ from .batch import _shared_fields
 from .svgd import JointDiBS
 
 
-def _validate(models, keys):
+def _validate(models, keys, who="sample_joint_batch"):
     models = list(models)
     keys = [random.as_key(k) for k in keys]
     if not models:
         return models, keys
     if len(keys) != len(models):
-        raise ValueError(f"sample_joint_batch: {len(models)} models but {len(keys)} keys")
+        raise ValueError(f"{who}: {len(models)} models but {len(keys)} keys")
     for i, m in enumerate(models):
         if not isinstance(m, JointDiBS):
-            raise ValueError(f"sample_joint_batch: every model must be a JointDiBS, model {i} is a {type(m).__name__} "
-                             "(MarginalDiBS models: sample_batch)")
+            raise ValueError(f"{who}: every model must be a JointDiBS, model {i} is a {type(m).__name__} "
+                             f"(MarginalDiBS models: {'sample_sweep' if who == 'sample_joint_sweep' else 'sample_batch'})")
         if m.likelihood_model._dibs_likelihood != "lingauss":
-            raise ValueError(f"sample_joint_batch: model {i} has a {type(m.likelihood_model).__name__} likelihood; only LinearGaussian "
+            raise ValueError(f"{who}: model {i} has a {type(m.likelihood_model).__name__} likelihood; only LinearGaussian "
                              "problems are batched on data sets of their own (DenseNonlinearGaussian: sample_chains for several seeds on "
                              "one data set, or sample() per problem)")
         if getattr(m, "precision", "float32") != "float32":
-            raise ValueError("sample_joint_batch: float64 models are not supported (the float64 engine runs one problem; use sample())")
+            raise ValueError(f"{who}: float64 models are not supported (the float64 engine runs one problem; use sample())")
     return models, keys
 
 
@@ -60,13 +60,17 @@ def sample_joint_batch(models, *, keys, n_particles, steps, n_dim_particles=None
     return _run(models, keys, cfgs[0], n_particles, n_dim, steps, callback, callback_every)
 
 
-def _run(models, keys, cfg, n_particles, n_dim, steps, callback, callback_every):
+def _run(models, keys, cfg, n_particles, n_dim, steps, callback, callback_every, hparams=None):
+    """The B problems in one chains engine created from ``cfg``; ``hparams``: per problem a ChainHparams (sample_joint_sweep), or None
+    for the configuration's values.  Sets every model's ``last_state`` and returns the list of ``(g, theta)``."""
     B, d = len(models), models[0].n_vars
     cfg.reserved_i[2] = B
     eng = Engine(cfg)
     try:
         for i, m in enumerate(models):
             eng.set_data_problem(i, m.x, m.interv_mask if m.interv_mask.any() else None, None)
+            if hparams is not None:
+                eng.set_chain_hparams(i, hparams[i])
         eng.init_particles_batch(np.stack([np.asarray(k, np.uint32).reshape(2) for k in keys]))
         for m in models:
             if m.latent_prior_std is None:

@@ -286,7 +286,40 @@ int dibs_engine_get_problem_hparams(dibs_engine* e, int32_t p, dibs_problem_hpar
  * share one data set); n_obs must equal dibs_config.n_observations (it selects LDS sizes and kernels), c must be in [0, C), bge_mean_obs
  * NULL; a chain's data may be given again until the particles are initialised (init_particles_batch / set_state / run), not after -- as
  * dibs_engine_set_problem_hparams; dibs_engine_run with some but not all chains given data fails and names the first missing chain (with
- * no data at all: "dibs_engine_set_data has not been called"). */
+ * no data at all: "dibs_engine_set_data has not been called").
+ * PER-CHAIN HYPER-PARAMETERS (a hyper-parameter grid of one joint model in one engine; the Python side is
+ * dibs_amd.inference.sample_joint_sweep; JointDiBS + LinearGaussian).  The eight double fields of dibs_config below -- the seven of
+ * dibs_problem_hparams and h_theta, the bandwidth of the parameter kernel -- may differ between the chains.  A chain whose values were never
+ * set has the configuration's.  Everything else stays shared: sizes, N, S, Sa, prior / optimizer / estimator kind, tau, scale_*, rng_layout
+ * and the likelihood's obs_noise, mean_edge, sig_edge.  Chain c ends bit-identical to a standalone engine configured with c's values.
+ *   dibs_engine_set_chain_hparams(e, c, hp)   validated as dibs_engine_create validates the shared value (Erdos-Renyi: edge probability in
+ *       (0, 1); latent_prior_std <= 0: the default 1/sqrt(k)); only before dibs_engine_init_particles_batch / dibs_engine_set_state / the
+ *       first dibs_engine_run (latent_prior_std of chain c enters chain c's initial draw; the device table is written once, then).
+ *   dibs_engine_get_chain_hparams(e, c, hp)   the values in force (latent_prior_std as given, <= 0 meaning the default)
+ * Values equal to the configuration's are accepted on every chains engine and change nothing: the step is launch for launch the one of an
+ * engine on which nothing was set.  Values that DIFFER from the configuration's
+ *   - are accepted only on a LinearGaussian engine (the DenseNonlinearGaussian kernels have no per-chain form),
+ *   - need n_vars <= 64, n_dim <= 64 and an acyclicity pipe other than bf16 (the sizes whose edge, acyclicity and tail kernels have
+ *     table-reading forms, as for dibs_engine_set_problem_hparams),
+ *   - need per-chain data: dibs_engine_set_data_problem for every chain (a sweep over one data set uploads it C times, C * N * d * 8 bytes
+ *     with the mask).  dibs_engine_set_data on an engine that holds differing values is refused, and so are differing values on an engine
+ *     whose data came through dibs_engine_set_data; dibs_engine_run with differing values and no per-chain data fails and says so.
+ * With differing values a step forms every chain's annealed alpha and beta on the device (in double, as the host does for a standalone
+ * engine), the edge, acyclicity, tail and kernel-matrix launches read the chain's row of the device table, and the per-chain forms of the
+ * LinearGaussian kernels take alpha and score_function_baseline of the block's chain from it.  Every misuse fails with a message that
+ * starts "chains engine (n_chains > 1): " and names the call. */
+typedef struct dibs_chain_hparams {
+  double alpha_linear;
+  double beta_linear;
+  double h_latent;
+  double h_theta;
+  double stepsize;
+  double score_function_baseline;
+  double latent_prior_std;
+  double graph_prior_edges_per_node;
+} dibs_chain_hparams;
+int dibs_engine_set_chain_hparams(dibs_engine* e, int32_t c, const dibs_chain_hparams* hp);
+int dibs_engine_get_chain_hparams(dibs_engine* e, int32_t c, dibs_chain_hparams* hp);
 
 /* FLOAT64 ENGINE (no reference counterpart as such: the reference reaches double precision through JAX_ENABLE_X64,
  * dibs/models/nonlinearGaussian.py:183-185): dibs_config.reserved_i[1] = 64 makes the engine compute what the f64 build of the oracle
