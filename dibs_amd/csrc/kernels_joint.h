@@ -7,10 +7,15 @@
 #define GRAD_WCH 256  // weights are evaluated in chunks of this many samples (one double-precision exp per thread and chunk)
 // A sample is differentiated when its softmax weight is at least 2^-30.  The oracle (as round 5's kernels) keeps every weight that is
 // non-zero in float32, down to 1e-45; but a term w_s grad_s with w_s < 2^-30 is 64 times below the float32 resolution of the sum it is added to
-// (the weights sum to 1 and the samples' gradients are of one magnitude) -- the reference's own float32 logsumexp loses it the same way -- and
+// (the weights sum to 1; the samples' gradients are NOT of one magnitude -- a sample far down the weights has a parameter far from its optimum and
+// the larger gradient.  Measured, profiles/grad_weight_errors.txt: on the constructed weight profiles of tests/weight_states.py everything the cut
+// drops is at most 4.3e-8 of the sum; on the adversarial state -- theta at the ridge optimum, the kept samples' gradient rounding noise, every other
+// sample a factor 4 below the cut -- it is 8e-3 of the sum, where the float32 oracle itself is 0.2 off the float64 one) -- the reference's own float32 logsumexp loses it the same way -- and
 // late in a run of the LinearGaussian model such samples are the majority of the "weighted" ones: config 3 at step 1 500 has 12.4 samples per
 // particle with a non-zero weight in the theta estimator (worst particle 54) and 4.2 (24) with a weight of at least 2^-30 -- k_lin_grad
 // 271 -> 154 us; config 5 at step 300 keeps 16.2 of 16.7 (the weights of its saturated graphs really are spread): profiles/round6_late_breakdown.txt.
+// "Takes part" is !(w < GRAD_W_MIN) in every kernel and in the count of grad_softmax_stats: a NaN weight (a non-finite log-probability) takes
+// part and the particle's gradient is NaN, as in the reference -- never a silent zero.
 #define GRAD_W_MIN 9.313225746154785e-10f
 
 struct LinGeom {
@@ -162,7 +167,7 @@ __device__ __forceinline__ void grad_softmax_stats(const float* __restrict__ lp,
     sm += red[NW + w];
   }
   double cnt = 0.0;
-  for (int s = tid; s < S; s += NTHR) cnt += ((float)(exp((double)lp[s] - mx) / den) >= GRAD_W_MIN) ? 1.0 : 0.0;
+  for (int s = tid; s < S; s += NTHR) cnt += !((float)(exp((double)lp[s] - mx) / den) < GRAD_W_MIN) ? 1.0 : 0.0;  // (the ONE predicate: a NaN weight takes part)
   cnt = wave_sum_d(cnt);
   if (lane == 0) red[2 * NW + wave] = cnt;
   __syncthreads();

@@ -679,7 +679,7 @@ __global__ __launch_bounds__(64 * NW) void k_nn_grad(const float* __restrict__ x
       for (int i0 = 0; i0 < GRAD_WCH; i0 += 64) {
         const int i = i0 + lane;
         const float wv = s0 + i < S ? wch[i] : 0.f;
-        const bool has = wv >= GRAD_W_MIN;
+        const bool has = !(wv < GRAD_W_MIN);  // (NaN takes part: kernels_joint.h)
         const unsigned long long hb = __ballot(has), lt = (1ull << lane) - 1ull;
         const int ord = qq + __popcll(hb & lt);
         const bool mine = has && (ord % NS) == bz;

@@ -375,6 +375,59 @@ def grad_theta_likelihood(cfg, z, theta, t, subk, x, interv):  # dibs.py:488-551
     return out, dict(logprobs=logprobs, g_samples=g_samples)
 
 
+def estimator_keys(cfg, key, n_particles):
+    """(theta keys [M, 2], Z keys [M, 2]) that svgd_step hands to the estimators from the state key   svgd.py:695-703"""
+    ks = prng.split(np.asarray(key, np.uint32), n_particles + 1, cfg.rng_layout)
+    kz = prng.split(ks[0], n_particles + 1, cfg.rng_layout)
+    return ks[1:], kz[1:]
+
+
+def likelihood_sample_terms(cfg, mode, z, theta, t, subk, x, interv, samples=None):
+    """The S samples of one particle's estimator before the softmax: (logprobs [S], samples, terms) with terms[li][q] the term of sample
+    samples[q] (default: all) that the estimator weights by softmax(logprobs)  --  mode 'theta': d log p / d theta leaves (`grad_theta_likelihood`);
+    'reparam' / 'score': d / d scores [d, d] of log p(soft graph) / of log p(G_s | Z), the chain through scores = U V^T left to the caller
+    (`grad_z_likelihood_gumbel` / `grad_z_likelihood_score_function` without a baseline: alpha (G_s - P) off the diagonal).
+    `weighted_sample_sum` adds them up for ANY weight vector: a stage test hands it the softmax of the device's own log-probabilities."""
+    S, d = cfg.n_grad_mc_samples, z.shape[0]
+    alpha = cfg.alpha_linear * t
+    z = z.detach()
+    if mode == "theta":
+        graphs = sample_g(edge_probs(z, alpha), subk, S, cfg.rng_layout)
+    else:
+        _, subk_ = prng.split(subk, 2, cfg.rng_layout)
+        if mode == "score":
+            graphs = sample_g(edge_probs(z, alpha), subk_, S, cfg.rng_layout)
+        else:
+            eps = _t(prng.logistic(subk_, (S, d, d), cfg.rng_layout))
+            graphs = torch.stack([particle_to_soft_graph(z, eps[s], alpha, cfg.tau) for s in range(S)])
+    with torch.no_grad():
+        logprobs = torch.stack([log_joint_prob(cfg, graphs[s], theta, x, interv) for s in range(S)])
+    samples = list(range(S)) if samples is None else [int(s) for s in samples]
+    n_leaves = len(theta) if mode == "theta" else 1
+    terms = [[] for _ in range(n_leaves)]
+    for s in samples:
+        if mode == "theta":
+            th = [leaf.detach().clone().requires_grad_(True) for leaf in theta]
+            gr = torch.autograd.grad(log_joint_prob(cfg, graphs[s], th, x, interv), th, allow_unused=True)
+            for li in range(n_leaves):
+                terms[li].append(torch.zeros_like(theta[li]) if gr[li] is None else gr[li])
+        elif mode == "score":
+            terms[0].append(zero_diagonal(alpha * (graphs[s] - edge_probs(z, alpha))))
+        else:
+            sc = scores_uv(z).clone().requires_grad_(True)
+            soft = zero_diagonal(torch.sigmoid(cfg.tau * (eps[s] + alpha * sc)))
+            terms[0].append(torch.autograd.grad(log_joint_prob(cfg, soft, theta, x, interv), sc)[0])
+    shapes = [tuple(leaf.shape) for leaf in theta] if mode == "theta" else [(d, d)]
+    terms = [torch.stack(tl) if tl else torch.zeros((0,) + shapes[li], dtype=DT) for li, tl in enumerate(terms)]
+    return logprobs, samples, terms
+
+
+def weighted_sample_sum(terms, weights):
+    """sum_q weights[q] terms[li][q] per leaf (float64, sample order)"""
+    w = _t(weights)
+    return [(w.reshape((-1,) + (1,) * (tl.ndim - 1)) * tl).sum(0) for tl in terms]
+
+
 def acyclic_constr(mat, d):  # dibs/graph_utils.py:8-28
     M = torch.eye(d, dtype=DT) + mat / d
     return torch.trace(torch.linalg.matrix_power(M, d)) - d

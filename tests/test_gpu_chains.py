@@ -273,3 +273,13 @@ def test_sample_chains_marginal_model_goes_through_the_batched_engine():
         assert np.array_equal(out[c], g)
         for name in ("z", "v_z", "baseline", "key"):
             assert np.array_equal(m.last_chain_states[c][name], m.last_state[name]), (c, name)
+
+
+# ---- 10: chains whose particles have MANY weighted samples (tests/weight_states.py) -----------------------------------------------------
+# Every case above runs steps 0 .. 8 from the initial draw: one weighted sample per particle, the gradient kernels' one-block form.  Here
+# one launch holds a chain with one sample above the 2^-30 cut everywhere, a chain with 2 .. NS - 1 and a chain with more than NS (asserted
+# on the oracles by tests/test_weight_states_host.py): the shares of a particle are dealt, summed and counted per chain row.
+@pytest.mark.parametrize("name", ["lingauss_reparam", "lingauss_score", "densenn", "densenn_deep"])
+def test_chains_with_many_weighted_samples(c_oracle64, name):
+    import weight_states as W
+    W.assert_chains_match_standalone([W.build(case, c_oracle64) for case in W.CHAIN_CASES[name]])

@@ -344,3 +344,17 @@ def test_sample_joint_batch_equals_sequential_sample_with_callbacks():
             ds, ts, zs, ths = seen_s[i * n_chunks + ch]
             assert db is batch[i] and ds is seq[i] and tb == ts == (ch + 1) * every
             assert np.array_equal(zb, zs) and np.array_equal(thb, ths), (ch, i)
+
+
+# ---- per-chain data with MANY weighted samples (tests/weight_states.py) -------------------------------------------------------------------
+# Every case above runs from the initial draw: one weighted sample per particle.  Here chain c has its own data set AND a state built on it
+# with one sample above the 2^-30 cut everywhere (chain 0), 2 .. NS - 1 (chain 1, with interventions in the first case) and more than NS
+# (chain 2): the per-chain forms of k_lin_grad / k_ling_grad deal, sum and count a particle's shares.  GRAD_THETA, W_LIK after run(t, 1) and
+# the state after three further steps, bit for bit against standalone engines.
+@pytest.mark.parametrize("name", ["data_lingauss", "data_gram_n300"])
+def test_per_chain_data_with_many_weighted_samples(c_oracle64, monkeypatch, name):
+    import weight_states as W
+    bs = [W.build(case, c_oracle64) for case in W.CHAIN_CASES[name]]
+    if bs[0]["gram"]:
+        monkeypatch.setenv("DIBS_LIN_GRAM", "1")
+    W.assert_chains_match_standalone(bs, per_chain_data=True)

@@ -395,3 +395,13 @@ def test_sample_joint_sweep_equals_sequential_sample(with_callback):
                 ds, ts, zs, ths = seen_s[i * n_chunks + ch]
                 assert db is sweep[i] and ds is seq[i] and tb == ts == (ch + 1) * every
                 assert np.array_equal(zb, zs) and np.array_equal(thb, ths), (ch, i)
+
+
+# ---- per-chain values with MANY weighted samples (tests/weight_states.py) ------------------------------------------------------------------
+# alpha_linear and h_theta differ per chain; every chain's state is built with its own alpha so that chain 0 has one sample above the 2^-30
+# cut everywhere, chain 1 2 .. NS - 1 and chain 2 more than NS: the gradient kernels read this step's alpha from the chain's row of the
+# table while they deal and sum shares.  Bit for bit against standalone engines configured with the chain's values.
+def test_per_chain_values_with_many_weighted_samples(c_oracle64):
+    import weight_states as W
+    bs = [W.build(case, c_oracle64) for case in W.CHAIN_CASES["sweep_lingauss"]]
+    W.assert_chains_match_standalone(bs, hps=W.SWEEP_HPS)

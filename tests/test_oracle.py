@@ -179,3 +179,36 @@ def test_joint_densenn_step_cport_vs_autograd(c_oracle64, est, bias, act):
         assert rel_err(dbg["grad_z"], (aux["dz_lik"] + aux["dz_prior"]).numpy()) < 1e-6
         assert rel_err(cs["z"], st.z.numpy()) < 1e-6
         assert rel_err(cs["theta"], flat(st.theta)) < 1e-9
+
+
+@pytest.mark.parametrize("model,est", [("lingauss", "reparam"), ("lingauss", "score"), ("densenn", "reparam"), ("densenn", "score")])
+def test_sample_terms_reproduce_the_estimators(model, est):
+    """likelihood_sample_terms + weighted_sample_sum (the reference of tests/test_gpu_grad_weights.py, which takes the weights as given)
+    with the softmax of the oracle's own log-probabilities IS the estimator: theta leaves and the Z gradient to 1e-12, late in a run
+    (alpha = 4: graphs of a particle overlap, several samples carry weight)."""
+    d, M, N, S, t = 5, 2, 30, 12, 80
+    rng = np.random.default_rng(1)
+    x = _xt(rng.normal(size=(N, d)).astype(np.float32))
+    interv = _xt((rng.random((N, d)) < 0.1).astype(np.float64))
+    ocfg = O.Config(joint=True, likelihood=model, alpha_linear=0.05, grad_estimator_z=est, n_grad_mc_samples=S,
+                    lin=O.LinGaussParams(obs_noise=3.0), nn=O.DenseNNParams(hidden_layers=(3,), activation="tanh", obs_noise=3.0))
+    st = O.init_state(ocfg, prng.PRNGKey(4), M, d)
+    kth, kz = O.estimator_keys(ocfg, st.key, M)
+    for m in range(M):
+        ref, aux = O.grad_theta_likelihood(ocfg, st.z[m], st.theta[m], t, kth[m], x, interv)
+        lp, _, terms = O.likelihood_sample_terms(ocfg, "theta", st.z[m], st.theta[m], t, kth[m], x, interv)
+        assert torch.equal(lp, aux["logprobs"])
+        w = torch.softmax(lp, 0)
+        assert (w > 1e-6).sum() >= 2, w
+        for a, b in zip(O.weighted_sample_sum(terms, w), ref):
+            assert rel_err(a.numpy(), b.numpy()) < 1e-12
+        f = O.grad_z_likelihood_gumbel if est == "reparam" else O.grad_z_likelihood_score_function
+        ref, _, aux = f(ocfg, st.z[m], st.theta[m], st.sf_baseline[m], t, kz[m], x, interv)
+        lp, _, terms = O.likelihood_sample_terms(ocfg, est, st.z[m], st.theta[m], t, kz[m], x, interv)
+        assert torch.equal(lp, aux["logprobs"])
+        (wl,) = O.weighted_sample_sum(terms, torch.softmax(lp, 0))
+        dz = torch.stack([wl @ st.z[m][..., 1], wl.T @ st.z[m][..., 0]], -1)   # scores = U V^T: dU = W V, dV = W^T U
+        assert rel_err(dz.numpy(), ref.numpy()) < 1e-12
+        # a subset of the samples: the same terms
+        _, idx, sub = O.likelihood_sample_terms(ocfg, est, st.z[m], st.theta[m], t, kz[m], x, interv, samples=[7, 2])
+        assert idx == [7, 2] and torch.equal(sub[0], terms[0][[7, 2]])
