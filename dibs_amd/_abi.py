@@ -6,7 +6,7 @@ ABI_VERSION = 2
 MAX_HIDDEN_LAYERS = 8
 
 LIK = {"bge": 0, "lingauss": 1, "densenn": 2}
-PRIOR = {"er": 0, "sf": 1, "uniform": 2}
+PRIOR = {"er": 0, "sf": 1, "uniform": 2, "edgewise": 3}
 EST = {"score": 0, "reparam": 1}
 OPT = {"gd": 0, "rmsprop": 1}
 RNG = {"legacy": 0, "partitionable": 1}

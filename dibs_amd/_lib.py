@@ -24,7 +24,7 @@ EXPORTS = [
     "dibs_engine_comm_init_ipc", "dibs_engine_flag_fallbacks", "dibs_engine_debug_drop_next_flag",
     "dibs_engine_set_data_problem", "dibs_engine_init_particles_batch", "dibs_engine_get_keys", "dibs_engine_set_keys",
     "dibs_engine_set_problem_hparams", "dibs_engine_get_problem_hparams",
-    "dibs_engine_set_chain_hparams", "dibs_engine_get_chain_hparams",
+    "dibs_engine_set_chain_hparams", "dibs_engine_get_chain_hparams", "dibs_engine_set_edge_prior",
     "dibs_engine_set_data_f64", "dibs_engine_set_state_f64", "dibs_engine_get_state_f64", "dibs_engine_precision",
 ]
 
@@ -108,6 +108,7 @@ def load():
     lib.dibs_engine_get_problem_hparams.argtypes = [vp, i32, C.POINTER(ProblemHparams)]
     lib.dibs_engine_set_chain_hparams.argtypes = [vp, i32, C.POINTER(ChainHparams)]
     lib.dibs_engine_get_chain_hparams.argtypes = [vp, i32, C.POINTER(ChainHparams)]
+    lib.dibs_engine_set_edge_prior.argtypes = [vp, vp]
     lib.dibs_engine_set_data_f64.argtypes = [vp, vp, vp, vp]
     lib.dibs_engine_set_state_f64.argtypes = [vp] + [vp] * 6
     lib.dibs_engine_get_state_f64.argtypes = [vp] + [vp] * 6

@@ -341,7 +341,10 @@ extern "C" int dibs_engine_create(const dibs_config* cfg, void* stream, dibs_eng
     return fail("Unknown gradient estimator");  // dibs.py:318 (ValueError)
   if (c.optimizer != DIBS_OPT_GD && c.optimizer != DIBS_OPT_RMSPROP) return fail("unknown optimizer");  // svgd.py:122
   if (c.likelihood < 0 || c.likelihood > 2) return fail("unknown likelihood model");
-  if (c.graph_prior < 0 || c.graph_prior > 2) return fail("unknown graph prior");
+  if (c.graph_prior < 0 || c.graph_prior > DIBS_PRIOR_EDGEWISE) return fail("unknown graph prior");
+  if (c.graph_prior == DIBS_PRIOR_EDGEWISE && c.reserved_i[0] > 1)
+    return fail("batched engine (n_problems > 1): the edge-wise graph prior is not supported (the table-reading tail kernel has no edge-wise "
+                "form, and per-problem tables are not built)");
   if (!c.joint && c.likelihood != DIBS_LIK_BGE)
     return fail("MarginalDiBS needs a marginal likelihood (BGe)");
   if (c.joint && c.likelihood == DIBS_LIK_BGE)
@@ -406,7 +409,7 @@ extern "C" int dibs_engine_destroy(dibs_engine* e) {
   if (e->stream2) hipStreamSynchronize(e->stream2);
   void* ptrs[] = {e->z, e->vz, e->theta, e->vtheta, e->baseline, e->baseline2, e->scores, e->probs, e->eas, e->thr, e->w_lik, e->acyc_part, e->w_acyc,
                   e->logprobs_z, e->logprobs_th, e->pack, e->kz, e->kt, e->phi_z, e->phi_th, e->counters, e->masks,
-                  e->node_scores, e->x, e->mask, e->bq.list, e->bq.counts, e->soft_ds, e->acyc_big, e->w_tot, e->join_flag, e->fork_flag, e->carry_bak, e->soft_tri, e->ksum, e->kpart, e->kmat_ctr, e->bcarry, e->bkeys_lik, e->bkeys_prior, e->bkeys_theta, e->hp};
+                  e->node_scores, e->x, e->mask, e->bq.list, e->bq.counts, e->soft_ds, e->acyc_big, e->w_tot, e->join_flag, e->fork_flag, e->carry_bak, e->soft_tri, e->ksum, e->kpart, e->kmat_ctr, e->bcarry, e->bkeys_lik, e->bkeys_prior, e->bkeys_theta, e->hp, e->edge_tab, e->edge_tab64};
   for (void* p : ptrs)
     if (p) hipFree(p);
   joint_free(&e->jw);
@@ -598,8 +601,51 @@ extern "C" int dibs_engine_get_chain_hparams(dibs_engine* e, int32_t c, dibs_cha
   return 0;
 }
 
+// ---- edge-wise graph prior (include/dibs_hip.h, EDGE-WISE GRAPH PRIOR) --------------------------------------------------------------------
+extern "C" int dibs_engine_set_edge_prior(dibs_engine* e, const double* edge_probs) {
+  const std::string pre = "dibs_engine_set_edge_prior: ";
+  if (!e || !edge_probs) return fail(pre + "null engine or argument");
+  if (e->cfg.graph_prior != DIBS_PRIOR_EDGEWISE)
+    return fail(pre + "this engine's graph prior is not edge-wise (dibs_config.graph_prior must be DIBS_PRIOR_EDGEWISE)");
+  const int d = e->d;
+  const size_t dd = (size_t)d * d;
+  for (int i = 0; i < d; ++i)
+    for (int j = 0; j < d; ++j) {
+      const double p = edge_probs[(size_t)i * d + j];
+      if (i != j && !(p > 0.0 && p < 1.0)) {  // (NaN fails both comparisons)
+        char buf[160];
+        snprintf(buf, sizeof buf, "entry (%d, %d) = %g: every off-diagonal edge probability must be finite and strictly inside (0, 1)", i, j, p);
+        return fail(pre + buf);
+      }
+    }
+  HIP_OK(hipSetDevice(e->cfg.device_id));
+  HIP_OK(hipStreamSynchronize(e->stream));  // (the staging buffer of an earlier call is free; kernels of a step driven from outside are done)
+  if (e->f64) e->edge_host64.resize(dd);
+  else e->edge_host32.resize(dd);
+  for (int i = 0; i < d; ++i)
+    for (int j = 0; j < d; ++j) {
+      const double p = edge_probs[(size_t)i * d + j];
+      const double l = i == j ? 0.0 : log(p) - log(1 - p);  // (er_log_odds)
+      if (e->f64) e->edge_host64[(size_t)i * d + j] = l;
+      else e->edge_host32[(size_t)i * d + j] = (float)l;
+    }
+  if (e->f64) {
+    if (!e->edge_tab64) HIP_OK(hipMalloc((void**)&e->edge_tab64, dd * 8));  // (the copy below fills all of it)
+    HIP_OK(hipMemcpyAsync(e->edge_tab64, e->edge_host64.data(), dd * 8, hipMemcpyHostToDevice, e->stream));
+  } else {
+    if (!e->edge_tab) HIP_OK(hipMalloc((void**)&e->edge_tab, dd * 4));
+    HIP_OK(hipMemcpyAsync(e->edge_tab, e->edge_host32.data(), dd * 4, hipMemcpyHostToDevice, e->stream));
+  }
+  e->edge_tab_set = true;
+  return 0;
+}
+
 int batch_hp_commit(dibs_engine* e) {
   if (e->hp_final) return 0;
+  if (e->chains && e->cfg.graph_prior == DIBS_PRIOR_EDGEWISE && chains_hp_differ(e))
+    return fail("chains engine (n_chains > 1): the edge-wise graph prior is not supported together with per-chain hyper-parameters that differ "
+                "from the configuration's (dibs_engine_set_chain_hparams): the table-reading tail kernel has no edge-wise form, and per-problem "
+                "tables are not built");
   std::vector<ProblemHP> tab((size_t)e->B);
   for (int p = 0; p < e->B; ++p) tab[(size_t)p] = derive_problem_hp(e, e->hp_host[(size_t)p]);
   HIP_OK(hipMemcpy(e->hp, tab.data(), tab.size() * sizeof(ProblemHP), hipMemcpyHostToDevice));
@@ -704,6 +750,7 @@ extern "C" int dibs_engine_run(dibs_engine* e, int32_t t_start, int32_t n_steps)
     return fail("chains engine (n_chains > 1): dibs_engine_run: some chain's hyper-parameters differ from the configuration's "
                 "(dibs_engine_set_chain_hparams), which needs per-chain data: dibs_engine_set_data_problem has not been called for every chain");
   if (!e->has_data) return fail("dibs_engine_set_data has not been called");
+  if (need_edge_prior(e)) return 1;
   if (e->chains) {
     HIP_OK(hipSetDevice(e->cfg.device_id));
     if (batch_hp_commit(e)) return 1;

@@ -332,6 +332,7 @@ extern "C" int dibs_engine_run_sharded(dibs_engine* e, int32_t t_start, int32_t 
   if (refuse_chains(e, "the sharded entry points (chains are not sharded over ranks)")) return 1;
   if (e->B > 1) return fail("batched engine: a batch is not sharded over ranks");
   if (!e->has_data) return fail("dibs_engine_set_data has not been called");
+  if (need_edge_prior(e)) return 1;
   if (e->n_comms < 1) return fail("dibs_engine_comm_init has not been called");
   if (overlapped && e->n_comms < 2) return fail("the overlapped exchange needs two communicators (dibs_engine_comm_init with n_ids = 2)");
   HIP_OK(hipSetDevice(e->cfg.device_id));

@@ -99,6 +99,7 @@ int step_f64(dibs_engine* e, int t) {
   a.beta = c.beta_linear * t;
   a.tau = c.tau;
   a.er_c = er_log_odds(c);
+  a.prior_tab = e->edge_tab64;  // (DIBS_PRIOR_EDGEWISE: present, dibs_engine_run asks need_edge_prior)
   const double sigz = c.latent_prior_std > 0 ? c.latent_prior_std : (double)(1.0f / sqrtf((float)e->k));  // (the oracle's latent_std)
   a.inv_sig2 = 1.0 / (sigz * sigz);
   a.sfb = c.score_function_baseline;

@@ -2,6 +2,7 @@
 // struct, error / allocation / timing helpers, and the declarations of the internals that cross files.  No __global__ definitions: a kernel
 // header whose kernels are not templates is compiled into ONE unit (kernels_marginal.h, kernels_tail.h: engine_step.hip; exchange_ipc.h:
 // engine_comm.hip -- dibs_allow_lds keys its table on a kernel's host address) and gives every other file its structs and LDS sizes only.
+// (The block of kernels_tail.h is also compiled under k_particle_grad_batch in tu_batch.hip and k_particle_grad_edge in tu_tail_edge.hip.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -138,6 +139,13 @@ struct dibs_engine {
   int kmat_ns_max = 0;     // 0: the direct kernel k_kmat; otherwise the largest nsplit kpart has room for
   unsigned int* kmat_ctr = nullptr;  // one counter per tile (units riding in k_particle_grad: the last unit of a tile writes the entries)
   float* ksum = nullptr;  // joint models: kz + kt, formed by the k_kmat launch of kt (the weight matrix of the SVGD transform as ONE scalar-loadable array)
+  // edge-wise graph prior (DIBS_PRIOR_EDGEWISE, dibs_engine_set_edge_prior): log odds [d][d], diagonal 0, as the engine's precision has them
+  // (float: k_particle_grad_edge; double: k64_grad); allocated by the first call
+  float* edge_tab = nullptr;
+  double* edge_tab64 = nullptr;
+  bool edge_tab_set = false;
+  std::vector<float> edge_host32;  // staging of the stream-ordered copy
+  std::vector<double> edge_host64;
   uint32_t* thr;
   uint64_t* masks;
   BgeQueues bq;
@@ -240,6 +248,11 @@ inline double er_log_odds(const dibs_config& c) {
   if (c.graph_prior != DIBS_PRIOR_ER) return 0.0;
   const double p = er_edge_prob(c);
   return log(p) - log(1 - p);
+}
+
+// edge-wise graph prior: every entry point that evaluates the latent prior asks this first (never a zero prior in place of a missing table)
+inline int need_edge_prior(const dibs_engine* e) {
+  return e->cfg.graph_prior == DIBS_PRIOR_EDGEWISE && !e->edge_tab_set ? fail("dibs_engine_set_edge_prior has not been called") : 0;
 }
 
 // ---- profiling helpers -----------------------------------------------------------------------
@@ -356,6 +369,8 @@ void batch_launch_edge_scores(hipStream_t st, const float* z, float* scores, uin
                               int Mloc, int d, int k, int dpad, int ldk);
 void batch_launch_tail(hipStream_t st, const TailArgs& ta, const ProblemHP* hp, int pM, int Mloc, size_t lds);
 void batch_launch_acyc_power(const AcycLaunch& a, const ProblemHP* hp, int pM);
+// ---- tu_tail_edge.hip: k_particle_grad with the table of an edge-wise graph prior in place of the Erdos-Renyi constant ----
+void edge_launch_tail(hipStream_t st, const TailArgs& ta, const float* tab, int blocks, size_t lds);
 // ---- tu_batch.hip: the chain-aware launches of step_chains (keys, block-diagonal kernel matrices) ----
 void chains_launch_keys(hipStream_t st, Key2* carry, Key2* keys_theta, Key2* keys_lik, Key2* keys_prior, int C, int M, int layout);
 void chains_launch_kmat(hipStream_t st, bool tiled, const float* x, size_t len, float* kout, int C, int M, float scale, float h, const float* kadd,

@@ -292,8 +292,12 @@ static void launch_tail(dibs_engine* e, const RowTarget& rt, const TailOpts& o) 
                      (float)c.h_latent, e->kz, nullptr, nullptr, e->kmat_ctr};
     lds_g = lds > kmat_tile_lds_bytes() ? lds : kmat_tile_lds_bytes();
   }
-  allow_lds(k_particle_grad, lds_g);
-  hipLaunchKernelGGL(k_particle_grad, dim3(e->Mloc + o.nrider), dim3(TAIL_NT), lds_g, e->stream, ta);
+  if (ta.prior_kind == DIBS_PRIOR_EDGEWISE) {  // (the table exists: need_edge_prior at every entry point)
+    edge_launch_tail(e->stream, ta, e->edge_tab, e->Mloc + o.nrider, lds_g);
+  } else {
+    allow_lds(k_particle_grad, lds_g);
+    hipLaunchKernelGGL(k_particle_grad, dim3(e->Mloc + o.nrider), dim3(TAIL_NT), lds_g, e->stream, ta);
+  }
   if (e->w_tot) {
     const size_t lb = backproject_big_lds(e->d);
     allow_lds(k_backproject_big, lb);
@@ -774,6 +778,7 @@ extern "C" int dibs_engine_step_local(dibs_engine* e, int32_t t, void* send_dev)
   if (refuse_chains(e, "dibs_engine_step_local (only dibs_engine_run steps it)")) return 1;
   if (e->B > 1) return fail("batched engine: only dibs_engine_run steps it");
   if (!e->has_data) return fail("dibs_engine_set_data has not been called");
+  if (need_edge_prior(e)) return 1;
   HIP_OK(hipSetDevice(e->cfg.device_id));
   latch_flags(e);
   // send_dev holds only this rank's rows: [Mloc, E]; kernels index rows by global particle id
@@ -803,6 +808,7 @@ extern "C" int dibs_engine_step_local_grads(dibs_engine* e, int32_t t, void* gra
   if (refuse_chains(e, "dibs_engine_step_local_grads (only dibs_engine_run steps it)")) return 1;
   if (e->B > 1) return fail("batched engine: only dibs_engine_run steps it");
   if (!e->has_data) return fail("dibs_engine_set_data has not been called");
+  if (need_edge_prior(e)) return 1;
   HIP_OK(hipSetDevice(e->cfg.device_id));
   latch_flags(e);
   // rows [grad_z | grad_theta] of this rank's particles, stride Ev; kernels index rows by global particle id
@@ -853,6 +859,7 @@ extern "C" int dibs_engine_eval_gradients(dibs_engine* e, int32_t t, const uint3
   if (refuse_chains(e, "dibs_engine_eval_gradients")) return 1;
   if (e->B > 1) return fail("batched engine: dibs_engine_eval_gradients is not supported");
   if (!e->has_data) return fail("dibs_engine_set_data has not been called");
+  if (need_edge_prior(e)) return 1;
   const dibs_config& c = e->cfg;
   const bool want_lik = keys_lik != nullptr || keys_theta != nullptr, want_prior = keys_prior != nullptr;
   if (c.joint && want_lik && (!keys_lik || !keys_theta)) return fail("joint model: pass the keys of the theta AND the Z estimator (both run in one pass)");

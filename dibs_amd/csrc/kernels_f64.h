@@ -240,6 +240,7 @@ __global__ __launch_bounds__(256) void k64_grad(F64Args a) {
       const double dp = a.alpha * P[o] * (1.0 - P[o]);
       if (a.prior == DIBS_PRIOR_ER) pr = a.er_c * dp;
       else if (a.prior == DIBS_PRIOR_SF) pr = -3.0 / (1.0 + colsum[j]) * dp;
+      else if (a.prior == DIBS_PRIOR_EDGEWISE) pr = a.prior_tab[o] * dp;
     }
     W[o] = a.w_lik[(size_t)m * dd + o] - a.beta * a.w_acyc[(size_t)m * dd + o] + pr;
   }

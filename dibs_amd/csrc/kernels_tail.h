@@ -147,8 +147,23 @@ __host__ inline size_t tail_lds_bytes(int d, int ldz, int S, int W, bool lik, in
   return tail_fixed_bytes(d, ldz, S, lik) + (lik ? (size_t)stage_cap * d * W * 8 : 0);
 }
 
-#if defined(DIBS_TU_STEP) || defined(DIBS_TU_BATCH)  // (tu_batch.hip: the block, under k_particle_grad_batch)
-__device__ __forceinline__ void particle_grad_block(const TailArgs& A) {
+// The block is ONE source text compiled in three units.  engine_step.hip and tu_batch.hip get the form they always got: the TAIL_TAB_*
+// macros expand to nothing and TAIL_PRIOR_TERM to the Erdos-Renyi / scale-free select.  tu_tail_edge.hip (DIBS_TU_TAIL_EDGE) gets the
+// edge-wise graph prior (DIBS_PRIOR_EDGEWISE): a second parameter `tab` [d][d], the log odds of edge i -> j (diagonal 0), whose element e is
+// requested in the prefetch group of pa / pp / pw and takes the place of A.er_c.
+#ifdef DIBS_TU_TAIL_EDGE
+#define TAIL_TAB_PARAM , const float* __restrict__ tab
+#define TAIL_TAB_DECL float ptab[TAIL_EPT];
+#define TAIL_TAB_LOAD(u, e) ptab[u] = (e) < dd ? tab[e] : 0.f;
+#define TAIL_PRIOR_TERM(u, dp) (A.prior_kind == DIBS_PRIOR_EDGEWISE ? ptab[u] * (dp) : (-3.0f / (1.0f + cs[j])) * (dp))
+#else
+#define TAIL_TAB_PARAM
+#define TAIL_TAB_DECL
+#define TAIL_TAB_LOAD(u, e)
+#define TAIL_PRIOR_TERM(u, dp) (A.prior_kind == 0 ? A.er_c * (dp) : (-3.0f / (1.0f + cs[j])) * (dp))
+#endif
+#if defined(DIBS_TU_STEP) || defined(DIBS_TU_BATCH) || defined(DIBS_TU_TAIL_EDGE)  // (tu_batch.hip: the block, under k_particle_grad_batch)
+__device__ __forceinline__ void particle_grad_block(const TailArgs& A TAIL_TAB_PARAM) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   if (A.kt.x != nullptr && (int)blockIdx.x >= A.n_part) {  // (block-uniform)
     kmat_tile_block(reinterpret_cast<float*>(smem_raw), A.kt, (int)blockIdx.x - A.n_part, (int)gridDim.x - A.n_part, (int)threadIdx.x);
@@ -180,12 +195,14 @@ __device__ __forceinline__ void particle_grad_block(const TailArgs& A) {
   const float* wag = A.w_acyc + (size_t)m * dd;
   float* wlg = A.w_lik + (size_t)m * dd;
   float pa[TAIL_EPT], pp[TAIL_EPT], pw[TAIL_EPT];
+  TAIL_TAB_DECL
 #pragma unroll
   for (int u = 0; u < TAIL_EPT; ++u) {
     const int e = u * TAIL_NT + tid;
     pa[u] = (e < dd && !A.join_flag) ? wag[e] : 0.f;
     pp[u] = e < dd ? pm[e] : 0.f;
     pw[u] = (e < dd && !lik) ? wlg[e] : 0.f;
+    TAIL_TAB_LOAD(u, e)
   }
   auto load_pa_joined = [&]() {  // (join_flag: called right behind the first block barrier)
     if (A.join_flag) {
@@ -429,6 +446,7 @@ __device__ __forceinline__ void particle_grad_block(const TailArgs& A) {
           pa[u] = e < dd ? tail_ld_joined(A, wag + e) : 0.f;
           pp[u] = e < dd ? pm[e] : 0.f;
           pw[u] = (e < dd && !lik) ? wlg[e] : 0.f;
+          TAIL_TAB_LOAD(u, e)
         }
       }
 #pragma unroll
@@ -455,7 +473,7 @@ __device__ __forceinline__ void particle_grad_block(const TailArgs& A) {
         float pr = 0.f;
         if (i != j && A.prior_kind != 2) {
           const float dp = A.alpha * p * (1.0f - p);
-          pr = A.prior_kind == 0 ? A.er_c * dp : (-3.0f / (1.0f + cs[j])) * dp;
+          pr = TAIL_PRIOR_TERM(u, dp);
         }
         const float wt_ = wl - A.beta * pa[u] + pr;
         if (big) A.w_tot[(size_t)m * dd + e] = wt_;
@@ -518,6 +536,10 @@ __global__ __launch_bounds__(TAIL_NT) void k_particle_grad_batch(TailArgs A, con
   particle_grad_block(A);
 }
 #endif  // DIBS_TU_BATCH
+#ifdef DIBS_TU_TAIL_EDGE
+// edge-wise graph prior (include/dibs_hip.h, dibs_engine_set_edge_prior): the same block with the [d][d] table of log odds
+__global__ __launch_bounds__(TAIL_NT) void k_particle_grad_edge(TailArgs A, const float* __restrict__ tab) { particle_grad_block(A, tab); }
+#endif  // DIBS_TU_TAIL_EDGE
 
 // ------------------------------------------------------------------------------------------------
 // K7c  phase C of k_particle_grad for sizes whose W, U, V do not fit in one block's LDS: grad = [W V, W^T U] - z / sigma^2 from W in

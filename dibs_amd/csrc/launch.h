@@ -62,6 +62,7 @@ struct F64Args {
   double* node_scores;   // [M][d][S]
   const double *R, *Nj, *gam;  // BGe statistics in double: R [n_mats][d][d], N_j [d], log_gamma_term [d][d + 1]
   const float* ltab;           // [2^23] logistic value of the f32 uniform (bits >> 9) (engine_f64.hip: f64_logistic_table)
+  const double* prior_tab;     // [d][d] DIBS_PRIOR_EDGEWISE: log odds of edge i -> j, diagonal 0 (dibs_engine_set_edge_prior); else null
 };
 __host__ __device__ inline size_t f64_bge_wave_bytes(int d) { return (size_t)d * 64 * 8 + 64 * 4; }
 __host__ __device__ inline size_t f64_acyc_lds_bytes(int dpad) { return (size_t)3 * dpad * (dpad + 1) * 8; }

@@ -53,6 +53,15 @@ class Engine:
         f = self.lib.dibs_engine_set_data_f64 if self.precision == 64 else self.lib.dibs_engine_set_data
         _lib.check(f(self._h, _ptr(x), _ptr(m), _ptr(mo)))
 
+    def set_edge_prior(self, edge_probs):
+        """The table of an edge-wise graph prior (include/dibs_hip.h, dibs_engine_set_edge_prior): ``edge_probs[i, j]`` = prior probability
+        of the edge i -> j, ``[d, d]``, diagonal ignored.  Only on an engine configured with ``graph_prior="edgewise"``; may be repeated
+        between runs."""
+        p = np.ascontiguousarray(edge_probs, np.float64)
+        if p.shape != (self.d, self.d):
+            raise ValueError(f"edge_probs must have shape ({self.d}, {self.d}), got {p.shape}")
+        _lib.check(self.lib.dibs_engine_set_edge_prior(self._h, _ptr(p)))
+
     # batched engine (n_problems > 1): per-problem data, particles and loop-carry keys
     def set_data_problem(self, p, x, interv_mask=None, bge_mean_obs=None):
         x = np.ascontiguousarray(x, np.float32)

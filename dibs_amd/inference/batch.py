@@ -26,6 +26,19 @@ def _shared_fields(cfg):
     return out
 
 
+def _edgewise(m):
+    return getattr(getattr(m, "graph_model", None), "_dibs_prior", None) == "edgewise"
+
+
+def _refuse_edgewise(models, who, engine):
+    """The engines whose tail kernel reads a per-problem table have no edge-wise form (include/dibs_hip.h, EDGE-WISE GRAPH PRIOR)."""
+    for i, m in enumerate(models):
+        if _edgewise(m):
+            raise ValueError(f"{who}: model {i} has an edge-wise graph prior (EdgePriorDAGDistribution), which {engine} does not "
+                             "support: per-problem tables are not built (use sample() per problem; JointDiBS models with one shared "
+                             "table: sample_chains / sample_joint_batch)")
+
+
 def _batchable(models, keys, who):
     """What sample_batch and sample_sweep (`who`) ask of their arguments alike: as many keys as models, every model a float32 MarginalDiBS
     with the score-function estimator.  Returns (models, keys) as lists."""
@@ -42,6 +55,7 @@ def _batchable(models, keys, who):
             raise ValueError(f"{who}: only the score-function estimator is batched (grad_estimator_z='score')")
         if getattr(m, "precision", "float32") != "float32":
             raise ValueError(f"{who}: float64 models are not batched (the float64 engine runs one problem; use sample())")
+    _refuse_edgewise(models, who, "the batched engine")
     return models, keys
 
 

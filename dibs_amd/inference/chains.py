@@ -75,6 +75,8 @@ def _run_chains(model, keys, n_particles, n_dim, steps, callback, callback_every
     eng = Engine(cfg)
     try:
         eng.set_data(model.x, model.interv_mask if model.interv_mask.any() else None, None)
+        if model.graph_model._dibs_prior == "edgewise":   # (one table: the chains share it)
+            eng.set_edge_prior(model.graph_model.edge_probs)
         eng.init_particles_batch(np.stack([np.asarray(k, np.uint32).reshape(2) for k in keys]))
         if model.latent_prior_std is None:
             model.latent_prior_std = float(np.float32(1.0) / np.sqrt(np.float32(n_dim)))

@@ -9,7 +9,7 @@ import numpy as np
 
 from .. import random
 from ..engine import Engine
-from .batch import _shared_fields
+from .batch import _edgewise, _shared_fields
 from .svgd import JointDiBS
 
 
@@ -51,6 +51,8 @@ def sample_joint_batch(models, *, keys, n_particles, steps, n_dim_particles=None
         diff = [k for k in ref if ref[k] != got[k]]
         if c.n_observations != cfgs[0].n_observations:
             diff.append("n_observations")
+        if _edgewise(models[0]) and _edgewise(models[i]) and not np.array_equal(models[0].graph_model.log_odds, models[i].graph_model.log_odds):
+            diff.append("edge_probs")   # (the table of an edge-wise graph prior: one per engine)
         if diff:
             raise ValueError(f"sample_joint_batch: model {i} differs from model 0 in {', '.join(diff)} (a batch shares every size, the "
                              "number of observations and every hyper-parameter; only data, interventions and keys differ)")
@@ -67,6 +69,8 @@ def _run(models, keys, cfg, n_particles, n_dim, steps, callback, callback_every,
     cfg.reserved_i[2] = B
     eng = Engine(cfg)
     try:
+        if _edgewise(models[0]):   # (one table: sample_joint_batch has compared the models')
+            eng.set_edge_prior(models[0].graph_model.edge_probs)
         for i, m in enumerate(models):
             eng.set_data_problem(i, m.x, m.interv_mask if m.interv_mask.any() else None, None)
             if hparams is not None:

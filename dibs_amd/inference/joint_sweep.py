@@ -7,7 +7,7 @@ dibs_engine_set_chain_hparams).
 size, code path or buffer.  Everything else is shared as in ``sample_joint_batch`` (the number of observations included).  Entry i of
 the result equals ``models[i].sample(key=keys[i], ...)`` bit for bit.  A grid over one data set uploads it once per grid point."""
 from .._abi import JOINT_SWEEPABLE, chain_hparams
-from .batch import _shared_fields
+from .batch import _refuse_edgewise, _shared_fields
 from .joint_batch import _run, _validate
 from .svgd import MarginalDiBS
 
@@ -22,6 +22,7 @@ def _plan(models, keys, n_particles, n_dim_particles):
         if isinstance(m, MarginalDiBS):
             raise ValueError(f"sample_joint_sweep: model {i} is a MarginalDiBS; a grid of marginal models is sample_sweep")
     models, keys = _validate(models, keys, "sample_joint_sweep")
+    _refuse_edgewise(models, "sample_joint_sweep", "the per-chain hyper-parameter tier of the chains engine")
     if not models:
         return keys, None, None, []
     n_dim = n_dim_particles or models[0].n_vars

@@ -52,7 +52,8 @@ class _SVGDBase(DiBS):
         self.graph_model = graph_model
         if not hasattr(graph_model, "_dibs_prior"):
             raise NotImplementedError("graph_model must be one of ErdosReniDAGDistribution, ScaleFreeDAGDistribution, "
-                                      "UniformDAGDistributionRejection (arbitrary callables cannot be lowered to the device)")
+                                      "UniformDAGDistributionRejection, EdgePriorDAGDistribution (arbitrary callables cannot be lowered "
+                                      "to the device)")
         lik = getattr(likelihood_model, "_dibs_likelihood", None)
         allowed = ("lingauss", "densenn") if self._joint else ("bge",)
         if lik not in allowed:
@@ -94,6 +95,8 @@ class _SVGDBase(DiBS):
         eng = Engine(self._make_config(n_particles, n_dim, **kw), stream=stream)
         eng.set_data(self.x if self._x_engine is None else self._x_engine, self.interv_mask if self.interv_mask.any() else None,
                      getattr(self.likelihood_model, "mean_obs", None))
+        if self.graph_model._dibs_prior == "edgewise":
+            eng.set_edge_prior(self.graph_model.edge_probs)
         return eng
 
     # ---- estimators of the reference's DiBS base, on the device (dibs.py:255-269, 295-321, 467-485, 626-658) ----

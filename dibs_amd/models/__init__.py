@@ -1,3 +1,3 @@
-from .graph import ErdosReniDAGDistribution, ScaleFreeDAGDistribution, UniformDAGDistributionRejection  # noqa: F401
+from .graph import EdgePriorDAGDistribution, ErdosReniDAGDistribution, ScaleFreeDAGDistribution, UniformDAGDistributionRejection  # noqa: F401
 from .linearGaussian import LinearGaussian, BGe  # noqa: F401
 from .nonlinearGaussian import DenseNonlinearGaussian  # noqa: F401

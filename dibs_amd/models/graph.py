@@ -106,3 +106,51 @@ class UniformDAGDistributionRejection:
 
     def unnormalized_log_prob_soft(self, *, soft_g):
         return 0.0
+
+
+class EdgePriorDAGDistribution:
+    """Independent edges with a prior probability of their own: p(G) ~ prod_{i != j} P_ij^g_ij (1 - P_ij)^(1 - g_ij), up to the constant
+    sum log(1 - P_ij), i.e. log p(G) = sum_{i != j} g_ij L_ij + const with L = log(P) - log(1 - P).  ``edge_probs[i, j]`` is the prior
+    probability of the edge i -> j, a ``[d, d]`` array whose diagonal is ignored.  ``ErdosReniDAGDistribution`` is the special case of equal
+    entries.  (No reference counterpart: the reference takes any traced ``graph_model`` object; this is the commonest custom one.)
+
+    Every off-diagonal entry must be finite and strictly inside (0, 1), as for the Erdos-Renyi prior: the log odds must be finite.
+    "Forbidden" and "required" edges are expressed as probabilities such as ``1e-6`` and ``1 - 1e-6`` (a tier ordering: ``1e-6`` for every
+    edge from a later tier into an earlier one).  This is a prior on the soft graph: it pushes the edge probabilities, but hard masking of
+    ``p(G | Z)`` -- graphs with a forbidden edge having probability exactly zero -- is not part of it."""
+    _dibs_prior = "edgewise"
+
+    def __init__(self, n_vars, edge_probs):
+        self.n_vars = int(n_vars)
+        p = np.array(edge_probs, np.float64)
+        if p.shape != (self.n_vars, self.n_vars):
+            raise ValueError(f"edge_probs must have shape ({self.n_vars}, {self.n_vars}), got {p.shape}")
+        for i in range(self.n_vars):
+            for j in range(self.n_vars):
+                if i != j and not (0.0 < p[i, j] < 1.0):   # (NaN fails both comparisons)
+                    raise ValueError(f"edge_probs[{i}, {j}] = {p[i, j]}: the entry ({i}, {j}) must be finite and strictly inside (0, 1) "
+                                     "(use e.g. 1e-6 / 1 - 1e-6 for forbidden / required edges)")
+        np.fill_diagonal(p, 0.5)   # (ignored; keeps the logs finite)
+        self.edge_probs = p
+        self.log_odds = np.log(p) - np.log(1.0 - p)
+        np.fill_diagonal(self.log_odds, 0.0)
+
+    def sample_G(self, key, return_mat=False):
+        """A random order of the variables, then edge i -> j with probability P_ij where i precedes j in it (both Threefry streams of
+        dibs_amd.random)."""
+        d = self.n_vars
+        k_order, k_edges = random.split(random.as_key(key))
+        order = random.permutation(k_order, d)
+        rank = np.empty(d, np.int64)
+        rank[order] = np.arange(d)
+        u = np.asarray(random.uniform(k_edges, (d, d)), np.float64)
+        return ((u < self.edge_probs) & (rank[:, None] < rank[None, :])).astype(np.int32)
+
+    def unnormalized_log_prob_single(self, *, g, j):
+        return float(np.sum(np.asarray(g, np.float64)[:, j] * self.log_odds[:, j]))
+
+    def unnormalized_log_prob(self, *, g):
+        return float(np.sum(np.asarray(g, np.float64) * self.log_odds))
+
+    def unnormalized_log_prob_soft(self, *, soft_g):
+        return self.unnormalized_log_prob(g=soft_g)

@@ -25,7 +25,7 @@ extern "C" {
 #define DIBS_MAX_HIDDEN_LAYERS 8
 
 enum { DIBS_LIK_BGE = 0, DIBS_LIK_LINGAUSS = 1, DIBS_LIK_DENSENN = 2 };
-enum { DIBS_PRIOR_ER = 0, DIBS_PRIOR_SF = 1, DIBS_PRIOR_UNIFORM = 2 };
+enum { DIBS_PRIOR_ER = 0, DIBS_PRIOR_SF = 1, DIBS_PRIOR_UNIFORM = 2, DIBS_PRIOR_EDGEWISE = 3 /* see dibs_engine_set_edge_prior */ };
 enum { DIBS_EST_SCORE = 0, DIBS_EST_REPARAM = 1 };
 enum { DIBS_OPT_GD = 0, DIBS_OPT_RMSPROP = 1 };
 enum { DIBS_RNG_LEGACY = 0, DIBS_RNG_PARTITIONABLE = 1 };
@@ -345,6 +345,22 @@ int dibs_engine_set_state_f64(dibs_engine* e, const double* z, const double* v_z
                               const uint32_t* key, const double* baseline);
 int dibs_engine_get_state_f64(dibs_engine* e, double* z, double* v_z, double* theta, double* v_theta, uint32_t* key, double* baseline);
 int dibs_engine_precision(const dibs_engine* e);
+
+/* EDGE-WISE GRAPH PRIOR (no reference counterpart as a class; in the reference any traced graph_model object is accepted, this is the
+ * commonest one: independent edges, each with a probability of its own).  dibs_config.graph_prior = DIBS_PRIOR_EDGEWISE and
+ *   dibs_engine_set_edge_prior(e, edge_probs)   edge_probs: f64 [d][d] row-major, edge_probs[i][j] = prior probability of the edge i -> j;
+ *       the diagonal is ignored, every other entry must be finite and strictly inside (0, 1) (the rule of the Erdos-Renyi prior: the
+ *       log odds must be finite; "forbidden" and "required" are probabilities such as 1e-6 and 1 - 1e-6 -- p(G | Z) is not masked).
+ * The soft log-prior is sum_{i != j} g_ij L_ij with L = log(p) - log(1 - p) formed in double (as the Erdos-Renyi constant is) and kept on
+ * the device as float (float32 engine) or double (float64 engine), diagonal 0; its derivative takes the place of the Erdos-Renyi constant
+ * in the per-particle gradient kernel, so a table with the Erdos-Renyi probability in every entry reproduces DIBS_PRIOR_ER bit for bit.
+ * The call may be repeated between runs (the copy is ordered on the engine's stream).  It fails on an engine whose prior is not
+ * DIBS_PRIOR_EDGEWISE, for a null argument and for an entry outside (0, 1), naming the entry.  Until it has been called, dibs_engine_run /
+ * run_sharded / step_local / step_local_grads / eval_gradients fail with "dibs_engine_set_edge_prior has not been called".
+ * One table per engine: the chains of a chains engine share it.  The batched marginal engine (n_problems > 1) refuses the prior at
+ * creation and a chains engine with per-chain hyper-parameters that differ refuses it when the particles are initialised: the
+ * table-reading kernels of those tiers have no edge-wise form, and per-problem tables are not built. */
+int dibs_engine_set_edge_prior(dibs_engine* e, const double* edge_probs);
 
 /* debugging / parity: copy a device buffer to the host (nbytes must match); theta size query */
 int dibs_engine_read_buffer(dibs_engine* e, int32_t which, void* host, int64_t nbytes);
