@@ -208,6 +208,16 @@ int joint_set_data(JointWork* w, const float* x, const int32_t* mask, int N, int
   const size_t n = (size_t)N * d;
   if (w->x) hipFree(w->x);
   if (w->mask) hipFree(w->mask);
+  // Gram matrices belong to the data set they were built from: the caller builds new ones (joint_lin_set_gram) when THIS data set takes the
+  // Gram path.  (dibs_score_graphs keeps one workspace for held-out sets of any row count: a set on the LDS-resident path scored after one
+  // on the Gram path was evaluated against the earlier set's matrices.)
+  if (w->gram) hipFree(w->gram);
+  if (w->ncnt) hipFree(w->ncnt);
+  w->x = nullptr;
+  w->mask = nullptr;
+  w->gram = nullptr;
+  w->ncnt = nullptr;
+  w->n_gram = 0;
   if (hipMalloc((void**)&w->x, n * 4) != hipSuccess) return 1;
   if (hipMalloc((void**)&w->mask, n * 4) != hipSuccess) return 1;
   if (hipMemcpy(w->x, x, n * 4, hipMemcpyHostToDevice) != hipSuccess) return 1;
