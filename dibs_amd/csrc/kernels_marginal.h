@@ -393,7 +393,9 @@ __global__ __launch_bounds__(256) void k_phi_update(const float* __restrict__ pa
         // (kz + kt) g - (2 / h) k_seg (x_b - x_a) as three multiply-adds whose kernel entries stay scalar operands: forming kz + kt or
         // (2 / h) k_seg first would be vector instructions on wave-uniform values (and, hoisted by hipcc, 230 VGPRs)
         // JOINT: kz points at the weight matrix kz + kt (k_kmat forms it), kt at the matrix of THIS segment (repulsion); both stay scalar
-        // operands.  xpc / xac carry the factor -(2 / h).
+        // operands.  xpc / xac carry the factor -(2 / h): the difference is one of two ROUNDED products, so its error is 6e-8 |x| (2 / h)
+        // where the marginal form has 6e-8 |x_b - x_a| -- measured 2.3e-6 of max |phi| at |x| / |x_a - x_b| = 40 (marginal form: 1.7e-7;
+        // tests/test_gpu_transform.py, phi4_joint_lin_d5_M33); it grows with that ratio and reaches 1e-5 near 200.
         const float* tp = kt + (size_t)a * M + b;
         const f32x2 k2 = f32x2{tp[0], two ? tp[1] : 0.f};
         acc2[q] = __builtin_elementwise_fma(k2, xpc - xa2[q], __builtin_elementwise_fma(k1, gp, acc2[q]));
@@ -455,8 +457,16 @@ __global__ __launch_bounds__(256) void k_phi_update(const float* __restrict__ pa
 // K8c  the same transform + optimizer step for MANY particles (M >= 256: config 4's 1 024, config 5's 256) as one GEMM on the f32 MFMA:
 //     -M phi_a(i) = sum_b ks[a,b] grad_b(i)  +  sum_b (-kr[a,b]) x_b(i)  +  x_a(i) sum_b kr[a,b],      ks = kz + kt,  kr = (2/h) kseg
 //   i.e. [ks | -kr] (Mloc x 2M) times [grad ; x] (2M x len) plus a rank-one term whose row sums are accumulated from the same LDS tiles.
-//   (k_phi_update evaluates kr (x_b - x_a) per pair on the vector ALU -- three instructions per packed FMA, 847 us at M = 1 024.  The
-//   regrouped sum differs by the rounding of c |x_a| per particle, ~1e-7 of the gradient's own magnitude; PHI within 1e-5 in the tests.)
+//   (k_phi_update evaluates kr (x_b - x_a) per pair on the vector ALU -- three instructions per packed FMA, 847 us at M = 1 024.)
+//   Regrouped like this the two x terms CANCEL once the particles share a common component: their rounding is that of kr |x|, not of
+//   kr |x_b - x_a|.  Measured on tests/transform_states.py's offset_cluster states (|x| / |x_a - x_b| = 40, kernel entries ~0.5, repulsion
+//   = phi; phi against the float64 reference fed the device's gradients, max-norm over max |phi|): 4.1e-5 at M = 272, 7.5e-5 at M = 1 024
+//   -- beyond the 1e-5 this comment used to claim from tests whose kr was ~0.  So both x terms are taken relative to a reference value:
+//       sum_b (-kr[a,b]) (x_b(i) - c(i))  +  (x_a(i) - c(i)) sum_b kr[a,b],        c = the segment of GLOBAL particle 0
+//   (row 0 of `pack`, which every rank holds: c, and with it every sum, is a function of the global state only).  x_b - c is one rounding of
+//   a difference whose size is the particles' distance.  Measured with it (profiles/transform_errors.txt): the same states 4.4e-7 / 6.6e-7,
+//   joint models <= 9.8e-7; worst case of the kernel 2.2e-6 (M = 319 in the gradient regime: 319-term float32 sums of either sign on the
+//   MFMA), where the float32 oracle has <= 6.7e-8 and k_phi_update <= 1.7e-7.  tests/test_gpu_transform.py holds the kernel to 8.8e-6.
 // Block = 64 particles x 64 elements, 4 waves (wave w: rows 16 w .. 16 w + 15, 1 x 4 MFMA tiles; 128-particle blocks leave 2.5 blocks per
 // CU at config 4 -- CUs with three set the time: 310 us against [see below] with five 64-particle blocks per CU), k-chunks of 32 particles, the next
 // chunk's tiles prefetched into registers while the current one is multiplied.  The accumulation order of every output element is a
@@ -500,6 +510,21 @@ __global__ __launch_bounds__(256) void k_phi_gemm(const float* __restrict__ pack
   float4 pb[2];
   const bool full_cols = vec_ok && i0 + PG_BN <= len;  // block-uniform
   const uint32_t aoff = (uint32_t)((a0 + la) * M + lk) * 4u;
+  // the reference value c(i) of the regrouped repulsion (header): the segment of GLOBAL particle 0, a row of `pack` that every rank holds,
+  // at this thread's four B-tile columns (clamped like the rows' loads; the clamped lanes' products are masked or never stored)
+  float4 cref;
+  {
+    const float* src = pack + val_off;
+    const int i = i0 + lc, last = len - 1;
+    if (full_cols) {
+      cref = *reinterpret_cast<const float4*>(src + i);
+    } else {
+      cref.x = src[i < last ? i : last];
+      cref.y = src[i + 1 < last ? i + 1 : last];
+      cref.z = src[i + 2 < last ? i + 2 : last];
+      cref.w = src[i + 3 < last ? i + 3 : last];
+    }
+  }
   auto fetch = [&](int ch) {
     const bool xhalf = ch >= nch;
     const int b0 = (xhalf ? ch - nch : ch) * PG_BK;
@@ -535,14 +560,17 @@ __global__ __launch_bounds__(256) void k_phi_gemm(const float* __restrict__ pack
       const float val = JOINT ? fmaf(st, pt[j], sz * pz[j]) : sz * pz[j];
       As[(la + 8 * j) * PG_LDA + lk] = bok ? val : 0.f;
     }
+    // (value half: x_b - c, one rounding of a difference of near-equal numbers instead of products of the particles' common component)
+    const float4 cs = xhalf ? cref : make_float4(0.f, 0.f, 0.f, 0.f);  // (block-uniform select; g - 0 is g)
     if (full_cols && b0 + PG_BK <= M) {  // (block-uniform)
 #pragma unroll
-      for (int u = 0; u < 2; ++u) *reinterpret_cast<float4*>(&Bs[(lb + 16 * u) * PG_LDB + lc]) = pb[u];
+      for (int u = 0; u < 2; ++u)
+        *reinterpret_cast<float4*>(&Bs[(lb + 16 * u) * PG_LDB + lc]) = make_float4(pb[u].x - cs.x, pb[u].y - cs.y, pb[u].z - cs.z, pb[u].w - cs.w);
     } else {
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         const int i = i0 + lc;
-        float4 q = pb[u];
+        float4 q = make_float4(pb[u].x - cs.x, pb[u].y - cs.y, pb[u].z - cs.z, pb[u].w - cs.w);
         const bool rok = b0 + lb + 16 * u < M;
         q.x = (rok && i < len) ? q.x : 0.f;
         q.y = (rok && i + 1 < len) ? q.y : 0.f;
@@ -624,7 +652,7 @@ __global__ __launch_bounds__(256) void k_phi_gemm(const float* __restrict__ pack
         const int i = i0 + 16 * tj + r;
         if (i >= len) continue;
         const float xv = pack[(size_t)(m0 + a) * pack_stride + val_off + i];
-        const float tot = fmaf(rsa, xv, acc[ti][tj][q]);
+        const float tot = fmaf(rsa, xv - pack[val_off + i], acc[ti][tj][q]);  // (x_a - c) sum_b kr_ab
         const float phi = -tot * inv_m;
         const size_t o = (size_t)a * len + i;
         if (phi_out) phi_out[o] = phi;
