@@ -30,6 +30,15 @@
 #define BGE_NPL1 2
 #define BGE_NPL2 2
 #define BGE_NQ 9  // queue tiers: q = (n + 3) / 4 - 1 for n <= 32, 8 for larger problems
+// waves (columns) per block of k_bge_sample.  Measured with the flat column index and the 22-register fast loop in place, bench.py --full
+// at the headline size, three runs each, alternating (profiles/sample_schedule.txt): 4 waves 5 402 .. 5 434 steps/s, the launch 57.1 us on
+// the event timer; 8 waves 5 430 .. 5 447, the launch 63.3 us (k_bge_chol beside the acyclicity kernel 79 us instead of 85); parent
+// commit 5 281 .. 5 302 / 60.5 us.  The two ranges overlap there; at config 2 (20 variables, 32 particles, the kernel-matrix riders in the
+// launch) 4 waves 24 126 .. 24 335 steps/s, 8 waves 22 438 .. 22 749, parent commit 23 502 .. 23 750.  4 stays, which also keeps the LDS
+// bound of dibs_engine_create as it was.
+#ifndef BGE_SAMPLE_WAVES
+#define BGE_SAMPLE_WAVES 4
+#endif
 
 struct BgeParams {
   const float* Rp;      // [n_mats, d+1, d+1]  R with a zero row / column d (index d = "no variable": padding rows of a tier)
@@ -106,33 +115,89 @@ __device__ __forceinline__ void bge_index_mask(uint64_t& w0, uint64_t& w1, int j
 }
 
 // ------------------------------------------------------------------------------------------------
-// K2  sampling + queueing.  grid = (ceil(d / WAVES) [+ kernel-matrix blocks], Mloc), block = 64 * WAVES
+// K2  sampling + queueing.  One wave per column (m, j) of the Mloc * d columns, dealt from a FLAT index: wave w of block b takes column
+//     c = WAVES * b + w, m = c / d, j = c % d -- every wave of the launch works (a (ceil(d / WAVES), Mloc) grid left the waves j >= d of
+//     each particle's last block with nothing but the barriers: 256 of 6 656 at the headline size), and a block may span two particles:
+//     the per-wave LDS area, the per-block tier counters and the one global atomicAdd per tier and block do not care.
+//     grid = ceil(Mloc d / WAVES) [+ Mloc * ceil(M / KMAT_BT) kernel-matrix blocks behind them], block = 64 * WAVES
 //     layouts: masks [Mloc][d][S][W] u64, node_scores [Mloc][d][S] f64
 //     SAMPLE = false: the parent sets are given (dibs_score_graphs), only the queueing runs
+//     Measured at the headline size (profiles/sample_schedule.txt): with the flat index and the 22-register fast instantiation (all 6 400
+//     waves resident, eight per SIMD would fit) the launch takes 57.1 us on the event timer, 60.5 before; the step 5 402 .. 5 434 steps/s,
+//     5 281 .. 5 302 before.  What remains above the 43 us of pure issue is the rounding of 6.25 columns per SIMD to 7 and the ends of a
+//     wave that do not issue; capping the blocks per CU with padded LDS changed nothing -- the dispatcher already spreads them.
 // ------------------------------------------------------------------------------------------------
 __host__ __device__ inline size_t bge_sample_wave_bytes(int d, int S, int W) {
   // masks[S*W] u64 | thr[d] | lim[d] | loc[S]
   return ((size_t)S * W * 8 + (size_t)2 * d * 4 + (size_t)S * 4 + 15) & ~(size_t)15;
 }
 
-template <int WAVES, bool SAMPLE, bool BATCH = false>
+// 32 rows (fewer in a column's last block) i0 .. i1 - 1 of the sample pair (p, p + S/2) in the legacy layout with 32-bit counters: element c
+// pairs with c + n/2 in one Threefry call.  The kernel is bound by VALU issue and this loop is most of it: per output bit one compare and
+// one add-with-carry (word = 2 * word + bit, i.e. rows arrive MSB first and the word is bit-reversed once at the end).  c0 / c1 advance by
+// d per row, so consecutive blocks of a column continue one counter sequence.
+// Live across a Threefry call: the four state words, c0, c1, A, B and the LDS address -- the limits are read BEHIND the call that needs
+// them and the loop is not unrolled, so that the kernel fits the register budget of eight waves per SIMD.
+__device__ __forceinline__ void bge_sample_rows32(const TfKeys& tk, const uint32_t* lims, int i0, int i1, uint32_t d, uint32_t& c0, uint32_t& c1,
+                                                  uint32_t& wa, uint32_t& wb) {
+  uint32_t A = 0u, B = 0u;
+  int i = i0;
+#pragma unroll 1
+  for (; i + 1 < i1; i += 2, c0 += 2u * d, c1 += 2u * d) {
+    // (Skipping the call of a row whose threshold is 0 or 2^23 -- both outputs of a call belong to one row -- was measured and
+    //  dropped: the wave-uniform test needs the limits before the call instead of after it, +2 .. 4 % on this loop, and neither
+    //  the first steps nor a sparse posterior (p ~ 1e-10: thr = 1, which must still be drawn) have such rows.)
+    uint32_t y0, y1, y2, y3;
+    threefry2x32_uk2(tk, c0, c1, c0 + d, c1 + d, y0, y1, y2, y3);
+    const uint32_t L = lims[i], L2 = lims[i + 1];
+    asm volatile("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(A) : "v"(y0), "v"(L) : "vcc");
+    asm volatile("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(B) : "v"(y1), "v"(L) : "vcc");
+    asm volatile("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(A) : "v"(y2), "v"(L2) : "vcc");
+    asm volatile("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(B) : "v"(y3), "v"(L2) : "vcc");
+  }
+  if (i < i1) {
+    uint32_t y0, y1;
+    threefry2x32_uk(tk, c0, c1, y0, y1);
+    const uint32_t L = lims[i];
+    asm volatile("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(A) : "v"(y0), "v"(L) : "vcc");
+    asm volatile("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(B) : "v"(y1), "v"(L) : "vcc");
+    c0 += d;
+    c1 += d;
+  }
+  wa = __brev(A) >> (32 - (i1 - i0));
+  wb = __brev(B) >> (32 - (i1 - i0));
+}
+
+// KMAT: the launch carries kernel-matrix riders (KmatFuse::z).  Their code needs twice the registers of the sampling loop, and a kernel's
+// register count is that of its greediest role: a launch without riders -- the headline step -- takes the instantiation without them.
+// FAST (bge_sample_fast): legacy layout, even S, at most two mask words, 32-bit counters -- the paired loop of bge_sample_rows32 and nothing
+// else, for the same reason: the generic paths (odd S, partitionable layout, W > 2) live in the instantiations of their own.
+__host__ __device__ inline bool bge_sample_fast(int d, int S, int W, int layout) {
+  return layout == 0 && (S & 1) == 0 && W <= 2 && (uint64_t)S * (uint64_t)d * (uint64_t)d < 0xFFFFFFFFull;
+}
+template <int WAVES, bool SAMPLE, bool BATCH = false, bool KMAT = false, bool FAST = false>
 __global__ __launch_bounds__(64 * WAVES) void k_bge_sample(const uint32_t* __restrict__ thr, uint64_t* __restrict__ masks,
                                                            double* __restrict__ node_scores, BgeParams bp, Key2 carry, int m0,
-                                                           int M_global, int d, int S, int W, int layout, BgeQueues qs, KmatFuse kf) {
+                                                           int M_global, int Mloc, int d, int S, int W, int layout, BgeQueues qs,
+                                                           KmatFuse kf) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   // (s_setprio 3 for this kernel and k_bge_chol -- the critical path of a step, beside an acyclicity kernel with slack -- was measured:
   //  4 200 vs 4 207 steps/s, no effect)
-  if (kf.z && (int)blockIdx.x >= kf.nbx) {  // kernel-matrix role (block-uniform; WAVES == 4): see KmatFuse
-    kmat_block(reinterpret_cast<float*>(smem_raw), kf.z, (size_t)kf.len, (size_t)0, kf.len, kf.kout, 0, kf.M, kf.scale, kf.h, 1,
-               (int)blockIdx.y, (int)blockIdx.x - kf.nbx);
+  if (KMAT && kf.z && (int)blockIdx.x >= kf.nbx) {  // kernel-matrix role (block-uniform): see KmatFuse.  Rider r = a * nbt + bt, behind the sampling blocks
+    if (WAVES > 4 && threadIdx.x >= 256) return;  // (kmat_block is written for four waves; a barrier does not wait for a wave that has ended)
+    const int r = (int)blockIdx.x - kf.nbx, nbt = (kf.M + KMAT_BT - 1) / KMAT_BT, a = r / nbt;
+    kmat_block(reinterpret_cast<float*>(smem_raw), kf.z, (size_t)kf.len, (size_t)0, kf.len, kf.kout, 0, kf.M, kf.scale, kf.h, 1, a, r - a * nbt);
     return;
   }
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (kf.pub_flag && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0)  // (see KmatFuse: the fork flag of the step)
+  const int tid = threadIdx.x, lane = tid & 63;
+  // (wave-uniform by construction; saying so keeps the column's indices, keys and addresses in scalar registers)
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  if (kf.pub_flag && blockIdx.x == 0 && tid == 0)  // (see KmatFuse: the fork flag of the step)
     __hip_atomic_store(kf.pub_flag, kf.pub_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const int m = blockIdx.y;
-  const int j = blockIdx.x * WAVES + wave;
-  const bool active = j < d;
+  const int col = (int)blockIdx.x * WAVES + wave;
+  const bool active = col < Mloc * d;  // (only the last block can hold idle waves)
+  const int m = active ? col / d : 0;
+  const int j = col - m * d;
   unsigned char* wbase = smem_raw + (size_t)wave * bge_sample_wave_bytes(d, S, W);
   uint64_t* mk = reinterpret_cast<uint64_t*>(wbase);
   uint32_t* thrs = reinterpret_cast<uint32_t*>(mk + (size_t)S * W);
@@ -166,6 +231,26 @@ __global__ __launch_bounds__(64 * WAVES) void k_bge_sample(const uint32_t* __res
     const Key2 kg = rng_split_row_uniform(kp, 2u, 1u, layout);
     const uint64_t dd = (uint64_t)d * d, nbits = (uint64_t)S * dd;
     if (!SAMPLE) {
+    } else if (FAST) {
+      // the hot path (bge_sample_rows32): one 64-bit word of the pair at a time, stored as soon as it is complete -- only the
+      // ceil(d / 32) live half-words are ever computed or kept.  (Four unrolled half-word blocks with their eight results alive to the
+      // end, in one loop with the generic pair path below -- whose counters the compiler keeps as a dozen induction variables -- took
+      // 90 registers without the riders, 113 with them: four waves per SIMD.)
+      const int hS = S >> 1;
+      const TfKeys tk = tf_keys(kg);
+      for (int p = lane; p < hS; p += 64) {
+        uint32_t c0 = (uint32_t)p * (uint32_t)dd + (uint32_t)j, c1 = c0 + (uint32_t)(nbits >> 1);
+#pragma unroll 1
+        for (int w = 0; w < W; ++w) {
+          const int i0 = 64 * w, i1 = d < i0 + 32 ? d : i0 + 32;
+          uint32_t alo, blo, ahi = 0u, bhi = 0u;
+          bge_sample_rows32(tk, lims, i0, i1, (uint32_t)d, c0, c1, alo, blo);
+          if (i0 + 32 < d) bge_sample_rows32(tk, lims, i0 + 32, d < i0 + 64 ? d : i0 + 64, (uint32_t)d, c0, c1, ahi, bhi);
+          const uint64_t f = w ? force1 : force0;
+          mk[p * W + w] = (((uint64_t)ahi << 32) | alo) | f;
+          mk[(p + hS) * W + w] = (((uint64_t)bhi << 32) | blo) | f;
+        }
+      }
     } else if (W > 2) {
       // n_vars > 128: plain word loop, one Threefry call per sampled bit whatever the layout (the fallback behind the constructor's
       // full range, not tuned)
@@ -179,62 +264,17 @@ __global__ __launch_bounds__(64 * WAVES) void k_bge_sample(const uint32_t* __res
           }
           mk[s * W + w] = a;
         }
-    } else if ((S & 1) == 0) {
+    } else if ((S & 1) == 0) {  // (partitionable layout, or counters beyond 32 bits)
       const int hS = S >> 1;
       for (int p = lane; p < hS; p += 64) {
         uint64_t a0 = 0, a1 = 0, b0 = 0, b1 = 0;
         const uint64_t cbase = (uint64_t)p * dd + j;
-        if (layout == 0 && nbits < 0xFFFFFFFFull) {
-          // legacy layout, 32-bit counters: element c pairs with c + n/2 in one Threefry call.  The kernel is bound by VALU
-          // issue and this loop is most of it: per output bit one compare and one add-with-carry (word = 2 * word + bit,
-          // i.e. rows arrive MSB first and the word is bit-reversed once at the end).
-          const TfKeys tk = tf_keys(kg);
-          uint32_t c0 = (uint32_t)cbase, c1 = (uint32_t)cbase + (uint32_t)(nbits >> 1);
-          uint32_t wa[4] = {0u, 0u, 0u, 0u}, wb[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-          for (int w32 = 0; w32 < 4; ++w32) {
-            const int i0 = w32 * 32;
-            if (i0 < d) {
-              const int i1 = d < i0 + 32 ? d : i0 + 32;
-              uint32_t A = 0u, B = 0u;
-              int i = i0;
-              for (; i + 1 < i1; i += 2, c0 += 2u * (uint32_t)d, c1 += 2u * (uint32_t)d) {
-                // (Skipping the call of a row whose threshold is 0 or 2^23 -- both outputs of a call belong to one row -- was measured and
-                //  dropped: the wave-uniform test needs the limits before the call instead of after it, +2 .. 4 % on this loop, and neither
-                //  the first steps nor a sparse posterior (p ~ 1e-10: thr = 1, which must still be drawn) have such rows.)
-                uint32_t y0, y1, y2, y3;
-                threefry2x32_uk2(tk, c0, c1, c0 + (uint32_t)d, c1 + (uint32_t)d, y0, y1, y2, y3);
-                const uint32_t L = lims[i], L2 = lims[i + 1];
-                asm volatile("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(A) : "v"(y0), "v"(L) : "vcc");
-                asm volatile("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(B) : "v"(y1), "v"(L) : "vcc");
-                asm volatile("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(A) : "v"(y2), "v"(L2) : "vcc");
-                asm volatile("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(B) : "v"(y3), "v"(L2) : "vcc");
-              }
-              if (i < i1) {
-                uint32_t y0, y1;
-                threefry2x32_uk(tk, c0, c1, y0, y1);
-                const uint32_t L = lims[i];
-                asm volatile("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(A) : "v"(y0), "v"(L) : "vcc");
-                asm volatile("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(B) : "v"(y1), "v"(L) : "vcc");
-                c0 += (uint32_t)d;
-                c1 += (uint32_t)d;
-              }
-              wa[w32] = __brev(A) >> (32 - (i1 - i0));
-              wb[w32] = __brev(B) >> (32 - (i1 - i0));
-            }
-          }
-          a0 = (((uint64_t)wa[1] << 32) | wa[0]) | force0;
-          b0 = (((uint64_t)wb[1] << 32) | wb[0]) | force0;
-          a1 = (((uint64_t)wa[3] << 32) | wa[2]) | force1;
-          b1 = (((uint64_t)wb[3] << 32) | wb[2]) | force1;
-        } else {
-          for (int i = 0; i < d; ++i) {
-            uint32_t y0, y1;
-            rng_bits_pair(kg, nbits, cbase + (uint64_t)i * d, layout, y0, y1);
-            const uint32_t t = thrs[i];
-            const uint64_t ba = (uint64_t)((y0 >> 9) < t) << (i & 63), bb = (uint64_t)((y1 >> 9) < t) << (i & 63);
-            if (i < 64) { a0 |= ba; b0 |= bb; } else { a1 |= ba; b1 |= bb; }
-          }
+        for (int i = 0; i < d; ++i) {
+          uint32_t y0, y1;
+          rng_bits_pair(kg, nbits, cbase + (uint64_t)i * d, layout, y0, y1);
+          const uint32_t t = thrs[i];
+          const uint64_t ba = (uint64_t)((y0 >> 9) < t) << (i & 63), bb = (uint64_t)((y1 >> 9) < t) << (i & 63);
+          if (i < 64) { a0 |= ba; b0 |= bb; } else { a1 |= ba; b1 |= bb; }
         }
         mk[p * W] = a0;
         mk[(p + hS) * W] = b0;

@@ -51,11 +51,14 @@ int main() {
     }
     printf("%-44s %7.1f us\n", name, best * 1e3);
   };
-  hipFuncSetAttribute((const void*)k_bge_sample<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+  // (flat grid: one wave per column of the M d, the riders -- M x ceil(M / KMAT_BT) blocks -- behind the sampling blocks)
+  const int nbx = (M * d + 3) / 4;
+  hipFuncSetAttribute((const void*)k_bge_sample<4, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+  hipFuncSetAttribute((const void*)k_bge_sample<4, true, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
   time("k_bge_sample, no kernel-matrix blocks", [&] {
-    hipLaunchKernelGGL((k_bge_sample<4, true>), dim3(13, M), dim3(256), lds, 0, d_thr, d_masks, d_ns, bp, Key2{1, 2}, 0, M, d, S, W, 0, qs, KmatFuse{nullptr, nullptr, 0, 0, 0, 0.f, 0.f}); });
+    hipLaunchKernelGGL((k_bge_sample<4, true, false, false, true>), dim3(nbx), dim3(256), lds, 0, d_thr, d_masks, d_ns, bp, Key2{1, 2}, 0, M, M, d, S, W, 0, qs, KmatFuse{nullptr, nullptr, 0, 0, 0, 0.f, 0.f}); });
   time("k_bge_sample + kernel-matrix blocks", [&] {
-    hipLaunchKernelGGL((k_bge_sample<4, true>), dim3(13 + 8, M), dim3(256), ldsk > lds ? ldsk : lds, 0, d_thr, d_masks, d_ns, bp, Key2{1, 2}, 0, M, d, S, W, 0, qs, KmatFuse{d_z, d_k, 5000, M, 13, 1.f, 5.f}); });
+    hipLaunchKernelGGL((k_bge_sample<4, true, false, true, true>), dim3(nbx + M * 8), dim3(256), ldsk > lds ? ldsk : lds, 0, d_thr, d_masks, d_ns, bp, Key2{1, 2}, 0, M, M, d, S, W, 0, qs, KmatFuse{d_z, d_k, 5000, M, nbx, 1.f, 5.f}); });
   time("Threefry calls only (same count)", [&] { hipLaunchKernelGGL(k_threefry_only, dim3(13, M), dim3(256), 0, 0, Key2{1, 2}, M, d, S, d_out); });
   return 0;
 }
