@@ -14,7 +14,8 @@
 //     registers);   A_ij -= U_ki^T U_kj   (both operands are registers: register r of a block X in accumulator layout IS the A operand of
 //     X^T for the k-slab {r, 4 + r, 8 + r, 12 + r}, and of Y the B operand for the same slab);
 //     block row k of T:   T_ki = -T_kk sum_{l = i .. k-1} U_lk^T T_li.
-//   * the matrix is kept as A - I (diagonal entries p^2 (R_vv - 1)): pivots minus one stay exact for small p, as in k_bge_soft_reg.
+//   * the matrix is kept as A - I (diagonal entries p^2 (R_vv - 1)): pivots minus one stay exact for small p, as in k_bge_soft_reg
+//     (measured: gradient entries of parents with p in 1e-7 .. 1e-3 within 7.4e-7 of their own size -- header of kernels_bge_soft.h).
 // LDS per wave 3.3 KB (k_bge_soft_reg: 13.4 KB): occupancy is set by registers.  Block algebra checked in tests/tools/bge_soft_blocked_emulation.py.
 #pragma once
 #ifndef DIBS_TU_BGE_SOFT
