@@ -26,6 +26,7 @@ EXPORTS = [
     "dibs_engine_set_problem_hparams", "dibs_engine_get_problem_hparams",
     "dibs_engine_set_chain_hparams", "dibs_engine_get_chain_hparams", "dibs_engine_set_edge_prior",
     "dibs_engine_set_data_f64", "dibs_engine_set_state_f64", "dibs_engine_get_state_f64", "dibs_engine_precision",
+    "dibs_debug_threefry",
 ]
 
 
@@ -113,6 +114,7 @@ def load():
     lib.dibs_engine_set_state_f64.argtypes = [vp] + [vp] * 6
     lib.dibs_engine_get_state_f64.argtypes = [vp] + [vp] * 6
     lib.dibs_engine_precision.argtypes = [vp]
+    lib.dibs_debug_threefry.argtypes = [C.c_uint32] * 4 + [vp, i32, vp]
     for name in EXPORTS:
         if name not in ("dibs_last_error", "dibs_abi_version", "dibs_engine_gather_elems_per_rank", "dibs_engine_plane_elems_per_rank",
                         "dibs_engine_buffer_bytes", "dibs_engine_theta_size"):

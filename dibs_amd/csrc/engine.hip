@@ -794,6 +794,41 @@ extern "C" int dibs_engine_debug_drop_next_flag(dibs_engine* e) {
   return 0;
 }
 
+// the device Threefry routines of rng.h on caller-given arguments (dibs_debug_threefry): thread i takes counter c0[i]
+__global__ __launch_bounds__(256) void k_debug_threefry(Key2 key, uint32_t half, uint32_t off_b, const uint32_t* __restrict__ c0, int n,
+                                                        uint32_t* __restrict__ out) {
+  const TfKeys tk = tf_keys(key);
+  half = tf_uniform(half);
+  off_b = tf_uniform(off_b);
+  for (int i = threadIdx.x; i < n; i += 256) {
+    uint32_t s0, s1, a0, a1, b0, b1;
+    threefry2x32_uh(tk, c0[i], 0u, half, s0, s1);
+    threefry2x32_uh2(tk, c0[i], 0u, off_b, half, a0, a1, b0, b1);
+    uint32_t* o = out + 6 * (size_t)i;
+    o[0] = s0; o[1] = s1; o[2] = a0; o[3] = a1; o[4] = b0; o[5] = b1;
+  }
+}
+extern "C" int dibs_debug_threefry(uint32_t k0, uint32_t k1, uint32_t half, uint32_t off_b, const uint32_t* c0, int32_t n, uint32_t* out) {
+  if (!c0 || !out || n < 0) return fail("dibs_debug_threefry: null argument or negative n");
+  if (n == 0) return 0;
+  uint32_t *dc = nullptr, *dout = nullptr;
+  HIP_OK(hipMalloc(&dc, (size_t)n * 4));
+  if (hipMalloc(&dout, (size_t)n * 24) != hipSuccess) {
+    hipFree(dc);
+    return fail("dibs_debug_threefry: hipMalloc failed");
+  }
+  hipError_t rc = hipMemcpy(dc, c0, (size_t)n * 4, hipMemcpyHostToDevice);
+  if (rc == hipSuccess) {
+    hipLaunchKernelGGL(k_debug_threefry, dim3(1), dim3(256), 0, 0, Key2{k0, k1}, half, off_b, dc, n, dout);
+    rc = hipGetLastError();
+  }
+  if (rc == hipSuccess) rc = hipMemcpy(out, dout, (size_t)n * 24, hipMemcpyDeviceToHost);
+  hipFree(dc);
+  hipFree(dout);
+  if (rc != hipSuccess) return fail(std::string("dibs_debug_threefry: ") + hipGetErrorString(rc));
+  return 0;
+}
+
 extern "C" int64_t dibs_engine_gather_elems_per_rank(const dibs_engine* e) { return e ? (int64_t)e->Mloc * e->E : 0; }
 
 extern "C" int dibs_engine_sync(dibs_engine* e) {

@@ -227,8 +227,8 @@ __device__ __forceinline__ void acyc_block(const float* __restrict__ scores, flo
               const float ea = fast ? expf(-as) : as;
               uint32_t y0, y1 = 0u;
               if (paired) {
-                const uint32_t c0 = (uint32_t)((uint64_t)sa * dd) + (uint32_t)(i * d + pj);
-                threefry2x32_uk(tk, c0, c0 + (uint32_t)(nbits >> 1), y0, y1);
+                // counter sa d d + i d + pj, i = pi0 + q R: the lane's part is pi0 d + pj
+                threefry2x32_uh(tk, (uint32_t)(pi0 * d + pj), (uint32_t)((uint64_t)sa * dd) + (uint32_t)(q * R * d), (uint32_t)(nbits >> 1), y0, y1);
               } else {
                 y0 = rng_bits_at(km, nbits, (uint64_t)sa * dd + (uint64_t)(i * d + pj), layout);
               }

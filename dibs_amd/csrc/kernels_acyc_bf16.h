@@ -229,8 +229,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
               const float as = alpha * sml[a * d + b];
               const float ea = fast ? expf(-as) : as;
               uint32_t y0, y1;
-              const uint32_t c0 = (uint32_t)((uint64_t)sa * dd) + (uint32_t)(a * d + b);
-              threefry2x32_uk(tk, c0, c0 + (uint32_t)(nbits >> 1), y0, y1);
+              // counter sa d d + a d + b, b = b0 + 16 tj + i: the lane's part is a d + b0
+              threefry2x32_uh(tk, (uint32_t)(a * d + b0), (uint32_t)((uint64_t)sa * dd) + (uint32_t)(16 * tj + i), (uint32_t)(nbits >> 1), y0, y1);
               if (fast) {
                 const float u0 = rng_uniform(y0, ulo, 1.0f), u1 = rng_uniform(y1, ulo, 1.0f);
                 // (saturated edges -- exp(-alpha s) below the rounding of the denominator, every step once alpha s > ~17 -- must give exactly
@@ -487,8 +487,8 @@ __global__ __launch_bounds__(64 * NT) void k_acyc_bfw(const float* __restrict__ 
               const float as = alpha * sml[a * d + b];
               const float ea = fast ? expf(-as) : as;
               uint32_t y0, y1;
-              const uint32_t c0 = (uint32_t)((uint64_t)sa * dd) + (uint32_t)(a * d + b);
-              threefry2x32_uk(tk, c0, c0 + (uint32_t)(nbits >> 1), y0, y1);
+              // counter sa d d + a d + b, b = b0 + 16 tj + i: the lane's part is a d + b0
+              threefry2x32_uh(tk, (uint32_t)(a * d + b0), (uint32_t)((uint64_t)sa * dd) + (uint32_t)(16 * tj + i), (uint32_t)(nbits >> 1), y0, y1);
               if (fast) {
                 const float u0 = rng_uniform(y0, ulo, 1.0f), u1 = rng_uniform(y1, ulo, 1.0f);
                 const float den0 = fmaf(1.0f - u0, ea, u0), den1 = fmaf(1.0f - u1, ea, u1);

@@ -268,8 +268,7 @@ __device__ __forceinline__ void acyc_hf_block(const float* __restrict__ scores, 
           if (ea_ != eb_) {
             const float ea = fast ? s_cur : alpha * s_cur;
             uint32_t y0, y1;
-            const uint32_t c0 = cbase + (uint32_t)e;
-            threefry2x32_uk(tk, c0, c0 + chalf, y0, y1);
+            threefry2x32_uh(tk, (uint32_t)tid, cbase + 256u * (uint32_t)k, chalf, y0, y1);  // counter cbase + e: only tid is the lane's
             if (fast) {
               const float u0 = rng_uniform(y0, ulo, 1.0f), u1 = rng_uniform(y1, ulo, 1.0f);
               // (saturated edges must give exactly 1 as the reference's sigmoid does: see k_acyc_bf)
@@ -581,8 +580,7 @@ __global__ __launch_bounds__(64 * NT) void k_acyc_hfw(const float* __restrict__ 
           if (ea_ != eb_) {
             const float ea = fast ? s_cur : alpha * s_cur;
             uint32_t y0, y1;
-            const uint32_t c0 = cbase + (uint32_t)e;
-            threefry2x32_uk(tk, c0, c0 + chalf, y0, y1);
+            threefry2x32_uh(tk, (uint32_t)tid, cbase + (uint32_t)(G::NTHR * k), chalf, y0, y1);  // counter cbase + e: only tid is the lane's
             if (fast) {
               const float u0 = rng_uniform(y0, ulo, 1.0f), u1 = rng_uniform(y1, ulo, 1.0f);
               const float den0 = fmaf(1.0f - u0, ea, u0), den1 = fmaf(1.0f - u1, ea, u1);

@@ -126,6 +126,9 @@ __device__ __forceinline__ void bge_index_mask(uint64_t& w0, uint64_t& w1, int j
 //     waves resident, eight per SIMD would fit) the launch takes 57.1 us on the event timer, 60.5 before; the step 5 402 .. 5 434 steps/s,
 //     5 281 .. 5 302 before.  What remains above the 43 us of pure issue is the rounding of 6.25 columns per SIMD to 7 and the ends of a
 //     wave that do not issue; capping the blocks per CU with padded LDS changed nothing -- the dispatcher already spreads them.
+//     With the 62-instruction Threefry of rng.h and the counters' wave-uniform part in scalar registers (133 vector instructions per
+//     iteration of the paired loop instead of 149, profiles/threefry_xad.txt): 53.9 us on the event timer where the parent commit took
+//     57.1 in the same session, the step 5 526 .. 5 549 steps/s against 5 423 .. 5 435.
 // ------------------------------------------------------------------------------------------------
 __host__ __device__ inline size_t bge_sample_wave_bytes(int d, int S, int W) {
   // masks[S*W] u64 | thr[d] | lim[d] | loc[S]
@@ -134,35 +137,44 @@ __host__ __device__ inline size_t bge_sample_wave_bytes(int d, int S, int W) {
 
 // 32 rows (fewer in a column's last block) i0 .. i1 - 1 of the sample pair (p, p + S/2) in the legacy layout with 32-bit counters: element c
 // pairs with c + n/2 in one Threefry call.  The kernel is bound by VALU issue and this loop is most of it: per output bit one compare and
-// one add-with-carry (word = 2 * word + bit, i.e. rows arrive MSB first and the word is bit-reversed once at the end).  c0 / c1 advance by
-// d per row, so consecutive blocks of a column continue one counter sequence.
-// Live across a Threefry call: the four state words, c0, c1, A, B and the LDS address -- the limits are read BEHIND the call that needs
+// one add-with-carry (word = 2 * word + bit, i.e. rows arrive MSB first and the word is bit-reversed once at the end).
+// The counter of row i is c0 + off, c0 = p d d + j the lane's part and off = i d the wave's: off advances by d per row in SCALAR registers
+// (consecutive blocks of a column continue one sequence), the Threefry routine adds it to the key words on the scalar unit, and no vector
+// instruction of the loop touches a counter.  The four compares of an iteration write four SGPR pairs and the four add-with-carry read
+// them, all in one asm statement: nothing for the compiler to separate with s_nop.
+// Live across a Threefry call: the four state words, c0, A, B and the LDS address -- the limits are read BEHIND the call that needs
 // them and the loop is not unrolled, so that the kernel fits the register budget of eight waves per SIMD.
-__device__ __forceinline__ void bge_sample_rows32(const TfKeys& tk, const uint32_t* lims, int i0, int i1, uint32_t d, uint32_t& c0, uint32_t& c1,
-                                                  uint32_t& wa, uint32_t& wb) {
+__device__ __forceinline__ void bge_sample_rows32(const TfKeys& tk, const uint32_t* lims, int i0, int i1, uint32_t d, uint32_t c0, uint32_t half,
+                                                  uint32_t& off, uint32_t& wa, uint32_t& wb) {
   uint32_t A = 0u, B = 0u;
   int i = i0;
 #pragma unroll 1
-  for (; i + 1 < i1; i += 2, c0 += 2u * d, c1 += 2u * d) {
+  for (; i + 1 < i1; i += 2, off += 2u * d) {
     // (Skipping the call of a row whose threshold is 0 or 2^23 -- both outputs of a call belong to one row -- was measured and
     //  dropped: the wave-uniform test needs the limits before the call instead of after it, +2 .. 4 % on this loop, and neither
     //  the first steps nor a sparse posterior (p ~ 1e-10: thr = 1, which must still be drawn) have such rows.)
     uint32_t y0, y1, y2, y3;
-    threefry2x32_uk2(tk, c0, c1, c0 + d, c1 + d, y0, y1, y2, y3);
+    threefry2x32_uh2(tk, c0, off, off + d, half, y0, y1, y2, y3);
     const uint32_t L = lims[i], L2 = lims[i + 1];
-    asm volatile("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(A) : "v"(y0), "v"(L) : "vcc");
-    asm volatile("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(B) : "v"(y1), "v"(L) : "vcc");
-    asm volatile("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(A) : "v"(y2), "v"(L2) : "vcc");
-    asm volatile("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(B) : "v"(y3), "v"(L2) : "vcc");
+    uint64_t q0, q1, q2, q3;
+    asm volatile(
+        "v_cmp_lt_u32_e64 %2, %6, %10\n\tv_cmp_lt_u32_e64 %3, %7, %10\n\tv_cmp_lt_u32_e64 %4, %8, %11\n\tv_cmp_lt_u32_e64 %5, %9, %11\n\t"
+        "v_addc_co_u32_e64 %0, %2, %0, %0, %2\n\tv_addc_co_u32_e64 %1, %3, %1, %1, %3\n\t"
+        "v_addc_co_u32_e64 %0, %4, %0, %0, %4\n\tv_addc_co_u32_e64 %1, %5, %1, %1, %5"
+        : "+v"(A), "+v"(B), "=&s"(q0), "=&s"(q1), "=&s"(q2), "=&s"(q3)
+        : "v"(y0), "v"(y1), "v"(y2), "v"(y3), "v"(L), "v"(L2));
   }
   if (i < i1) {
     uint32_t y0, y1;
-    threefry2x32_uk(tk, c0, c1, y0, y1);
+    threefry2x32_uh(tk, c0, off, half, y0, y1);
     const uint32_t L = lims[i];
-    asm volatile("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(A) : "v"(y0), "v"(L) : "vcc");
-    asm volatile("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(B) : "v"(y1), "v"(L) : "vcc");
-    c0 += d;
-    c1 += d;
+    uint64_t q0, q1;
+    asm volatile(
+        "v_cmp_lt_u32_e64 %2, %4, %6\n\tv_cmp_lt_u32_e64 %3, %5, %6\n\t"
+        "v_addc_co_u32_e64 %0, %2, %0, %0, %2\n\tv_addc_co_u32_e64 %1, %3, %1, %1, %3"
+        : "+v"(A), "+v"(B), "=&s"(q0), "=&s"(q1)
+        : "v"(y0), "v"(y1), "v"(L));
+    off += d;
   }
   wa = __brev(A) >> (32 - (i1 - i0));
   wb = __brev(B) >> (32 - (i1 - i0));
@@ -239,13 +251,15 @@ __global__ __launch_bounds__(64 * WAVES) void k_bge_sample(const uint32_t* __res
       const int hS = S >> 1;
       const TfKeys tk = tf_keys(kg);
       for (int p = lane; p < hS; p += 64) {
-        uint32_t c0 = (uint32_t)p * (uint32_t)dd + (uint32_t)j, c1 = c0 + (uint32_t)(nbits >> 1);
+        // counter of row i: c0 + i d, and its partner's c0 + i d + half -- only c0 differs between the lanes
+        const uint32_t c0 = (uint32_t)p * (uint32_t)dd + (uint32_t)j, half = (uint32_t)(nbits >> 1);
+        uint32_t off = 0u;
 #pragma unroll 1
         for (int w = 0; w < W; ++w) {
           const int i0 = 64 * w, i1 = d < i0 + 32 ? d : i0 + 32;
           uint32_t alo, blo, ahi = 0u, bhi = 0u;
-          bge_sample_rows32(tk, lims, i0, i1, (uint32_t)d, c0, c1, alo, blo);
-          if (i0 + 32 < d) bge_sample_rows32(tk, lims, i0 + 32, d < i0 + 64 ? d : i0 + 64, (uint32_t)d, c0, c1, ahi, bhi);
+          bge_sample_rows32(tk, lims, i0, i1, (uint32_t)d, c0, half, off, alo, blo);
+          if (i0 + 32 < d) bge_sample_rows32(tk, lims, i0 + 32, d < i0 + 64 ? d : i0 + 64, (uint32_t)d, c0, half, off, ahi, bhi);
           const uint64_t f = w ? force1 : force0;
           mk[p * W + w] = (((uint64_t)ahi << 32) | alo) | f;
           mk[(p + hS) * W + w] = (((uint64_t)bhi << 32) | blo) | f;

@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NT <= 4 ? 3
   auto element = [&](int e, uint32_t cbase, int off, float th, float ln, float aux) {
     if (off < 0) return;
     uint32_t y0, y1;
-    threefry2x32_uk(tk, cbase + (uint32_t)e, cbase + (uint32_t)e + half, y0, y1);
+    threefry2x32_uh(tk, (uint32_t)e, cbase, half, y0, y1);  // counter cbase + e: cbase and half are the wave's
     float g0, g1;
     if (soft) {
       if (fast) {  // sigmoid(eps + a), eps = log(u / (1 - u))  ==  u / (u + (1 - u) exp(-a))
@@ -389,7 +389,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
   auto element = [&](int e, uint32_t cbase, int off, float th, float ln, float aux) {
     if (off < 0) return;
     uint32_t y0, y1;
-    threefry2x32_uk(tk, cbase + (uint32_t)e, cbase + (uint32_t)e + half, y0, y1);
+    threefry2x32_uh(tk, (uint32_t)e, cbase, half, y0, y1);  // counter cbase + e: cbase and half are the wave's
     float g0, g1;
     if (soft) {
       if (fast) {

@@ -152,7 +152,7 @@ struct NNStep {
   int da, dj;  // block size = da * d + dj
 };
 // FAST: legacy PRNG layout with an even number of samples and S d d < 2^32 -- element e of sample s is word (s < S/2 ? 0 : 1) of the Threefry
-// call on counters (c, c + S d d / 2), c = (s mod S/2) d d + e: 32-bit counters, key schedule hoisted (threefry2x32_uk), and for tau = 1
+// call on counters (c, c + S d d / 2), c = (s mod S/2) d d + e: 32-bit counters, key schedule hoisted (threefry2x32_uh), and for tau = 1
 // sigmoid(eps + a) = u / (u + (1 - u) exp(-a)) on v_rcp_f32.  (The generic path -- 64-bit element index, layout switch, key schedule and an
 // IEEE division per element -- is 320 vector instructions per element, 50 k of the kernel's 66 k wave-instructions per sample at config 5.)
 template <bool FAST>
@@ -172,7 +172,7 @@ __device__ __forceinline__ float nn_build_graph_tab(float* GS, int mode, Key2 ke
       gv = 0.f;
       if (a != j) {
         uint32_t y0, y1;
-        threefry2x32_uk(tk, cbase + (uint32_t)e, cbase + (uint32_t)e + half, y0, y1);
+        threefry2x32_uh(tk, (uint32_t)e, cbase, half, y0, y1);  // counter cbase + e: cbase and half are the wave's
         const uint32_t y = hi ? y1 : y0;
         if (mode == LIN_MODE_Z_REPARAM) {
           const float as = alpha * sc_m[e];
@@ -411,7 +411,8 @@ __device__ __forceinline__ void nn_grad_build_graph(float* GS, int mode, Key2 ke
   } else {
     const int dd = d * d, hS = S >> 1;
     const bool hi = s >= hS;
-    const uint32_t cbase = (uint32_t)(hi ? s - hS : s) * (uint32_t)dd, half = (uint32_t)(nbits >> 1);
+    // (s comes from the block's sample list in LDS: the same for every thread, which the compiler cannot see)
+    const uint32_t cbase = tf_uniform((uint32_t)(hi ? s - hS : s) * (uint32_t)dd), half = (uint32_t)(nbits >> 1);
     const float ulo = tiny ? 1.17549435e-38f : 1.1920929e-07f;
     const float inv_d = 1.0f / (float)d;
     for (int e = tid; e < dd; e += nthr) {
@@ -419,7 +420,7 @@ __device__ __forceinline__ void nn_grad_build_graph(float* GS, int mode, Key2 ke
       float gv = 0.f;
       if (a != j) {
         uint32_t y0, y1;
-        threefry2x32_uk(tk, cbase + (uint32_t)e, cbase + (uint32_t)e + half, y0, y1);
+        threefry2x32_uh(tk, (uint32_t)e, cbase, half, y0, y1);  // counter cbase + e: cbase and half are the wave's
         const uint32_t y = hi ? y1 : y0;
         if (mode == LIN_MODE_Z_REPARAM) {
           const float as = alpha * sc_m[e];

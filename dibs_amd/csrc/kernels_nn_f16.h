@@ -277,7 +277,7 @@ __global__ __launch_bounds__(NHF_NTHR) void k_nn_logprobs_hf(const float* __rest
         if (j < d && j != a) {
           const int e = a * d + j;
           uint32_t y0, y1;
-          threefry2x32_uk(tk, cbase + (uint32_t)e, cbase + (uint32_t)e + half, y0, y1);
+          threefry2x32_uh(tk, (uint32_t)e, cbase, half, y0, y1);  // counter cbase + e: cbase and half are the wave's
           if constexpr (SOFT) {
             const float as = alpha * sc_m[e];
             if (fast) {  // sigmoid(eps + a), eps = log(u / (1 - u))  ==  u / (u + (1 - u) exp(-a))

@@ -199,7 +199,7 @@ __global__ __launch_bounds__(64 * NT) void k_nn_logprobs_hx(const float* __restr
       float g0 = 0.f, g1 = 0.f;
       if (a != jj) {
         uint32_t y0, y1;
-        threefry2x32_uk(tk, cbase + (uint32_t)e, cbase + (uint32_t)e + half, y0, y1);
+        threefry2x32_uh(tk, (uint32_t)e, cbase, half, y0, y1);  // counter cbase + e: cbase and half are the wave's
         if constexpr (SOFT) {
           const float as = alpha * sc_m[e];
           if (fast) {  // sigmoid(eps + a), eps = log(u / (1 - u))  ==  u / (u + (1 - u) exp(-a))

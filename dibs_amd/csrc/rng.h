@@ -37,10 +37,17 @@ DIBS_HD void threefry2x32(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, ui
 // the whole derivation on the scalar unit instead of spending ~70 VALU issue slots per Threefry call in every wave
 __device__ __forceinline__ Key2 rng_split_row_uniform(Key2 key, uint32_t num, uint32_t r, int layout);
 
-// Threefry for wave-uniform keys, as one fixed instruction sequence (67 VALU ops): the key schedule lives in SGPRs,
-// each injection is folded into the following round's add (v_add3_u32), and the optimiser cannot re-derive the first rounds
-// as extra induction variables (it did, at +50 % instructions, when this ran inside a counter loop).  The sampling kernels are
-// bound by VALU issue, so the instruction count of this routine is their speed.
+// Threefry for wave-uniform keys AND a wave-uniform counter offset, as one fixed instruction sequence of 62 VALU ops.  Callers in the
+// legacy layout draw on counters (c0 + off, c0 + off + half) where only c0 differs between the lanes, so:
+//   - the key schedule and the sums off + half + k1, off + k0 live in SGPRs (scalar unit);
+//   - the first injection is x1 = c0 + (off + half + k1), x0 = c0 + (off + k0) + x1: two instructions that only READ c0 -- a loop
+//     keeps its lane counter in one register and advances `off` on the scalar unit, no vector add or copy in front of a call;
+//   - every later x0 injection is folded into the following round's add (v_add3_u32), every later x1 injection into the xor of the round
+//     in front of it (v_xad_u32 D = (S0 ^ S1) + S2; measured at the rate of a plain VALU op, profiles/threefry_xad.txt);
+//   - the optimiser cannot re-derive the first rounds as extra induction variables (it did, at +50 % instructions, when this ran
+//     inside a counter loop).
+// All of these are identities mod 2^32, wraps included: the output is that of threefry2x32 bit for bit (tests/test_gpu_threefry_device.py).
+// The sampling kernels are bound by VALU issue, so the instruction count of this routine is their speed.
 struct TfKeys {
   uint32_t k0, k1, k2, k2p1, k0p2, k1p3, k2p4, k0p5;
 };
@@ -61,56 +68,79 @@ __device__ __forceinline__ TfKeys tf_keys(Key2 key) {
   K.k0p5 = K.k0 + 5u;
   return K;
 }
-#define TF_RA(r) "v_add_u32 %0, %0, %1\n\tv_alignbit_b32 %1, %1, %1, " #r "\n\tv_xor_b32 %1, %1, %0\n\t"
-#define TF_RI(ka, kb, r) "v_add_u32 %1, " kb ", %1\n\tv_add3_u32 %0, %0, " ka ", %1\n\tv_alignbit_b32 %1, %1, %1, " #r "\n\tv_xor_b32 %1, %1, %0\n\t"
-__device__ __forceinline__ void threefry2x32_uk(const TfKeys& K, uint32_t c0, uint32_t c1, uint32_t& o0, uint32_t& o1) {
+// a value the caller knows to be wave-uniform where the compiler cannot prove it (it then stays in a scalar register)
+__device__ __forceinline__ uint32_t tf_uniform(uint32_t v) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  uint32_t x0 = c0, x1 = c1;
-  // alignbit(x, x, 32 - r) == rotl(x, r)
+  return __builtin_amdgcn_readfirstlane(v);
+#else
+  return v;
+#endif
+}
+// alignbit(x, x, 32 - r) == rotl(x, r).  TF_RA: a round; TF_RX: a round whose xor carries the x1 injection kb that follows it; TF_RJ: the
+// round behind an injection, its add carrying the x0 injection ka.  Operands: %0 x0, %1 x1.
+#define TF_RA(r) "v_add_u32 %0, %0, %1\n\tv_alignbit_b32 %1, %1, %1, " #r "\n\tv_xor_b32 %1, %1, %0\n\t"
+#define TF_RX(kb, r) "v_add_u32 %0, %0, %1\n\tv_alignbit_b32 %1, %1, %1, " #r "\n\tv_xad_u32 %1, %1, %0, " kb "\n\t"
+#define TF_RJ(ka, r) "v_add3_u32 %0, %0, " ka ", %1\n\tv_alignbit_b32 %1, %1, %1, " #r "\n\tv_xor_b32 %1, %1, %0\n\t"
+// output words of the call on counters (c0 + off, c0 + off + half): off, half wave-uniform, c0 a pure input
+__device__ __forceinline__ void threefry2x32_uh(const TfKeys& K, uint32_t c0, uint32_t off, uint32_t half, uint32_t& o0, uint32_t& o1) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  uint32_t x0, x1;
+  const uint32_t s1 = off + half + K.k1, s0 = off + K.k0;
   asm volatile(
-      TF_RI("%2", "%3", 19) TF_RA(17) TF_RA(6) TF_RA(26)          /* x = c + (k0, k1); rounds 13 15 26 6 */
-      TF_RI("%3", "%5", 15) TF_RA(3) TF_RA(16) TF_RA(8)           /* += (k1, k2 + 1);  rounds 17 29 16 24 */
-      TF_RI("%4", "%6", 19) TF_RA(17) TF_RA(6) TF_RA(26)          /* += (k2, k0 + 2) */
-      TF_RI("%2", "%7", 15) TF_RA(3) TF_RA(16) TF_RA(8)           /* += (k0, k1 + 3) */
-      TF_RI("%3", "%8", 19) TF_RA(17) TF_RA(6) TF_RA(26)          /* += (k1, k2 + 4) */
-      "v_add_u32 %0, %4, %0\n\tv_add_u32 %1, %9, %1"            /* += (k2, k0 + 5) */
-      : "+v"(x0), "+v"(x1)
-      : "s"(K.k0), "s"(K.k1), "s"(K.k2), "s"(K.k2p1), "s"(K.k0p2), "s"(K.k1p3), "s"(K.k2p4), "s"(K.k0p5));
+      "v_add_u32 %1, %11, %2\n\tv_add3_u32 %0, %2, %10, %1\n\t"        /* x = c + (k0, k1) */
+      "v_alignbit_b32 %1, %1, %1, 19\n\tv_xor_b32 %1, %1, %0\n\t"      /* rounds 13 15 26 6 */
+      TF_RA(17) TF_RA(6) TF_RX("%5", 26)
+      TF_RJ("%3", 15) TF_RA(3) TF_RA(16) TF_RX("%6", 8)                 /* += (k1, k2 + 1);  rounds 17 29 16 24 */
+      TF_RJ("%4", 19) TF_RA(17) TF_RA(6) TF_RX("%7", 26)                /* += (k2, k0 + 2) */
+      TF_RJ("%12", 15) TF_RA(3) TF_RA(16) TF_RX("%8", 8)                /* += (k0, k1 + 3) */
+      TF_RJ("%3", 19) TF_RA(17) TF_RA(6) TF_RX("%9", 26)                /* += (k1, k2 + 4); the last xor carries k0 + 5 */
+      "v_add_u32 %0, %4, %0"                                            /* += k2 */
+      : "=v"(x0), "=&v"(x1)
+      : "v"(c0), "s"(K.k1), "s"(K.k2), "s"(K.k2p1), "s"(K.k0p2), "s"(K.k1p3), "s"(K.k2p4), "s"(K.k0p5), "s"(s0), "s"(s1), "s"(K.k0));
   o0 = x0;
   o1 = x1;
 #else  // host pass of the single-source compile: never executed
-  threefry2x32(K.k0, K.k1, c0, c1, o0, o1);
+  threefry2x32(K.k0, K.k1, c0 + off, c0 + off + half, o0, o1);
 #endif
 }
 #undef TF_RA
-#undef TF_RI
+#undef TF_RX
+#undef TF_RJ
 // two independent calls interleaved instruction by instruction (dependent VALU ops of one chain do not issue back to back
-// at full rate; two chains per wave fill the gaps)
+// at full rate; two chains per wave fill the gaps): counters (c0 + off_a, c0 + off_a + half) and (c0 + off_b, c0 + off_b + half).
+// Operands: %0 x0, %1 x1 (call a), %2 z0, %3 z1 (call b).
 #define TF2_RA(r) "v_add_u32 %0, %0, %1\n\tv_add_u32 %2, %2, %3\n\tv_alignbit_b32 %1, %1, %1, " #r "\n\tv_alignbit_b32 %3, %3, %3, " #r \
                   "\n\tv_xor_b32 %1, %1, %0\n\tv_xor_b32 %3, %3, %2\n\t"
-#define TF2_RI(ka, kb, r) "v_add_u32 %1, " kb ", %1\n\tv_add_u32 %3, " kb ", %3\n\tv_add3_u32 %0, %0, " ka ", %1\n\tv_add3_u32 %2, %2, " ka ", %3\n\t" \
-                          "v_alignbit_b32 %1, %1, %1, " #r "\n\tv_alignbit_b32 %3, %3, %3, " #r "\n\tv_xor_b32 %1, %1, %0\n\tv_xor_b32 %3, %3, %2\n\t"
-__device__ __forceinline__ void threefry2x32_uk2(const TfKeys& K, uint32_t ca0, uint32_t ca1, uint32_t cb0, uint32_t cb1, uint32_t& oa0,
+#define TF2_RX(kb, r) "v_add_u32 %0, %0, %1\n\tv_add_u32 %2, %2, %3\n\tv_alignbit_b32 %1, %1, %1, " #r "\n\tv_alignbit_b32 %3, %3, %3, " #r \
+                      "\n\tv_xad_u32 %1, %1, %0, " kb "\n\tv_xad_u32 %3, %3, %2, " kb "\n\t"
+#define TF2_RJ(ka, r) "v_add3_u32 %0, %0, " ka ", %1\n\tv_add3_u32 %2, %2, " ka ", %3\n\t" \
+                      "v_alignbit_b32 %1, %1, %1, " #r "\n\tv_alignbit_b32 %3, %3, %3, " #r "\n\tv_xor_b32 %1, %1, %0\n\tv_xor_b32 %3, %3, %2\n\t"
+__device__ __forceinline__ void threefry2x32_uh2(const TfKeys& K, uint32_t c0, uint32_t off_a, uint32_t off_b, uint32_t half, uint32_t& oa0,
                                                  uint32_t& oa1, uint32_t& ob0, uint32_t& ob1) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  uint32_t x0 = ca0, x1 = ca1, z0 = cb0, z1 = cb1;
+  uint32_t x0, x1, z0, z1;
+  const uint32_t hk = half + K.k1, a1 = off_a + hk, a0 = off_a + K.k0, b1 = off_b + hk, b0 = off_b + K.k0;
   asm volatile(
-      TF2_RI("%4", "%5", 19) TF2_RA(17) TF2_RA(6) TF2_RA(26)
-      TF2_RI("%5", "%7", 15) TF2_RA(3) TF2_RA(16) TF2_RA(8)
-      TF2_RI("%6", "%8", 19) TF2_RA(17) TF2_RA(6) TF2_RA(26)
-      TF2_RI("%4", "%9", 15) TF2_RA(3) TF2_RA(16) TF2_RA(8)
-      TF2_RI("%5", "%10", 19) TF2_RA(17) TF2_RA(6) TF2_RA(26)
-      "v_add_u32 %0, %6, %0\n\tv_add_u32 %2, %6, %2\n\tv_add_u32 %1, %11, %1\n\tv_add_u32 %3, %11, %3"
-      : "+v"(x0), "+v"(x1), "+v"(z0), "+v"(z1)
-      : "s"(K.k0), "s"(K.k1), "s"(K.k2), "s"(K.k2p1), "s"(K.k0p2), "s"(K.k1p3), "s"(K.k2p4), "s"(K.k0p5));
+      "v_add_u32 %1, %13, %4\n\tv_add_u32 %3, %15, %4\n\tv_add3_u32 %0, %4, %12, %1\n\tv_add3_u32 %2, %4, %14, %3\n\t"
+      "v_alignbit_b32 %1, %1, %1, 19\n\tv_alignbit_b32 %3, %3, %3, 19\n\tv_xor_b32 %1, %1, %0\n\tv_xor_b32 %3, %3, %2\n\t"
+      TF2_RA(17) TF2_RA(6) TF2_RX("%7", 26)
+      TF2_RJ("%5", 15) TF2_RA(3) TF2_RA(16) TF2_RX("%8", 8)
+      TF2_RJ("%6", 19) TF2_RA(17) TF2_RA(6) TF2_RX("%9", 26)
+      TF2_RJ("%16", 15) TF2_RA(3) TF2_RA(16) TF2_RX("%10", 8)
+      TF2_RJ("%5", 19) TF2_RA(17) TF2_RA(6) TF2_RX("%11", 26)
+      "v_add_u32 %0, %6, %0\n\tv_add_u32 %2, %6, %2"
+      : "=&v"(x0), "=&v"(x1), "=v"(z0), "=&v"(z1)
+      : "v"(c0), "s"(K.k1), "s"(K.k2), "s"(K.k2p1), "s"(K.k0p2), "s"(K.k1p3), "s"(K.k2p4), "s"(K.k0p5), "s"(a0), "s"(a1), "s"(b0), "s"(b1),
+        "s"(K.k0));
   oa0 = x0; oa1 = x1; ob0 = z0; ob1 = z1;
 #else
-  threefry2x32(K.k0, K.k1, ca0, ca1, oa0, oa1);
-  threefry2x32(K.k0, K.k1, cb0, cb1, ob0, ob1);
+  threefry2x32(K.k0, K.k1, c0 + off_a, c0 + off_a + half, oa0, oa1);
+  threefry2x32(K.k0, K.k1, c0 + off_b, c0 + off_b + half, ob0, ob1);
 #endif
 }
 #undef TF2_RA
-#undef TF2_RI
+#undef TF2_RX
+#undef TF2_RJ
 
 // element i of random_bits(key, n).  layout 0 = legacy (counts split in halves, concat(y0, y1)),
 // 1 = partitionable (counter (hi, lo) = i, y0 ^ y1).

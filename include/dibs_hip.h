@@ -154,6 +154,11 @@ int dibs_engine_flag_fallbacks(const dibs_engine* e);
 /* fault injection for the tests of that path: the next step that would publish the second stream's completion flag does not, so the polling
  * kernel runs into its bound (0.2 s) exactly once.  No effect on an engine that is not using the flags. */
 int dibs_engine_debug_drop_next_flag(dibs_engine* e);
+/* for the tests of the device Threefry routines (csrc/rng.h: wave-uniform key, half and offsets): one block evaluates, for every i < n, the
+ * single routine on counters (c0[i], c0[i] + half) and the paired routine on (c0[i], c0[i] + half) and (c0[i] + off_b, c0[i] + off_b + half),
+ * all sums mod 2^32, with key (k0, k1).  c0: host u32 [n]; out: host u32 [n][6] = {single y0, y1, pair a y0, y1, pair b y0, y1}.
+ * Uses the current device and its null stream; blocking. */
+int dibs_debug_threefry(uint32_t k0, uint32_t k1, uint32_t half, uint32_t off_b, const uint32_t* c0, int32_t n, uint32_t* out);
 
 /* multi-rank split of one _svgd_step (svgd.py:226-267): phase A = per-particle estimators for the local
  * shard + packing of [z | grad_z (| theta | grad_theta)] into the send buffer; the caller all-gathers

@@ -13,10 +13,11 @@ __global__ __launch_bounds__(256) void k_threefry_only(Key2 carry, int M, int d,
   const Key2 kg = rng_split_row_uniform(kp, 2u, 1u, 0);
   const TfKeys tk = tf_keys(kg);
   const uint32_t dd = d * d, nbits = S * dd;
-  uint32_t c0 = lane * dd + j, c1 = c0 + (nbits >> 1), acc = 0;
-  for (int i = 0; i + 1 < d; i += 2, c0 += 2u * d, c1 += 2u * d) {
+  const uint32_t c0 = lane * dd + j;
+  uint32_t off = 0, acc = 0;
+  for (int i = 0; i + 1 < d; i += 2, off += 2u * d) {
     uint32_t y0, y1, y2, y3;
-    threefry2x32_uk2(tk, c0, c1, c0 + d, c1 + d, y0, y1, y2, y3);
+    threefry2x32_uh2(tk, c0, off, off + d, nbits >> 1, y0, y1, y2, y3);
     acc ^= y0 ^ y1 ^ y2 ^ y3;
   }
   if (acc == 0x12345678u) out[0] = acc;

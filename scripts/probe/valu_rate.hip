@@ -1,5 +1,5 @@
 // VALU issue rate on gfx950: wave-instructions per cycle per SIMD for f32 FMA, integer add/xor/alignbit (Threefry mix), f64 FMA,
-// v_log_f32 / v_rsq_f32, with 1 / 2 / 4 / 8 waves per SIMD and 1 / 2 / 4 independent chains per wave.
+// v_log_f32 / v_rsq_f32, v_xad_u32, with 1 / 2 / 4 / 8 waves per SIMD and 1 / 2 / 4 independent chains per wave.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
@@ -26,6 +26,9 @@ __global__ void k(int iters, float* out) {
         if (KIND == 4) { asm volatile("v_rsq_f32 %0, %0" : "+v"(f[c])); }
         if (KIND == 5) { asm volatile("v_add3_u32 %0, %0, %1, %1" : "+v"(a[c]) : "v"(b[c])); }
         if (KIND == 6) { asm volatile("v_pk_fma_f32 %0, %0, %1, %1" : "+v"(g[c]) : "v"((double)m)); }
+        if (KIND == 7) { asm volatile("v_xor_b32 %0, %0, %1" : "+v"(a[c]) : "v"(b[c])); }
+        if (KIND == 8) { asm volatile("v_xad_u32 %0, %0, %1, %1" : "+v"(a[c]) : "v"(b[c])); }
+        if (KIND == 9) { asm volatile("v_xad_u32 %0, %0, %1, %2" : "+v"(a[c]) : "v"(b[c]), "s"(iters)); }  // (the Threefry form: key word in an SGPR)
       }
     }
   }
@@ -54,7 +57,13 @@ static void run(const char* name, int per_iter) {
   }
   printf("\n");
 }
-int main() {
+int main(int argc, char** argv) {
+  // Threefry's fused injection (D = (S0 ^ S1) + S2) beside a plain op and v_add3_u32: dependent chain, two and four interleaved chains
+  run<7, 1>("v_xor_b32", 1); run<7, 2>("v_xor_b32", 1); run<7, 4>("v_xor_b32", 1);
+  run<5, 1>("v_add3_u32", 1); run<5, 2>("v_add3_u32", 1);
+  run<8, 1>("v_xad_u32 vvv", 1); run<8, 2>("v_xad_u32 vvv", 1); run<8, 4>("v_xad_u32 vvv", 1);
+  run<9, 1>("v_xad_u32 vvs", 1); run<9, 2>("v_xad_u32 vvs", 1); run<9, 4>("v_xad_u32 vvs", 1);
+  if (argc > 1) return 0;  // (any argument: the integer group only)
   run<0, 1>("v_fma_f32", 1); run<0, 2>("v_fma_f32", 1); run<0, 4>("v_fma_f32", 1); run<0, 8>("v_fma_f32", 1);
   run<1, 1>("add/alignbit/xor", 3); run<1, 2>("add/alignbit/xor", 3); run<1, 4>("add/alignbit/xor", 3);
   run<5, 1>("v_add3_u32", 1); run<5, 4>("v_add3_u32", 1);
