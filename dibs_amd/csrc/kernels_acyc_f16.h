@@ -17,14 +17,18 @@
 // The f16 range (6e-5 .. 65504 normal) needs a scale per power.  All entries of a power of M = I + G~/d are >= 0 and P >= I, and
 //      max (P P) <= 64 max(P)^2,    max (M P) <= rowsum(M) max(P) < 2 max(P),
 // so the shift of the NEXT power is chosen from the exact maximum of the CURRENT one -- which every wave knows one barrier late for
-// free: a wave's row maximum travels through LDS with the image it stores (8 v_max3 + 6 DPP steps per product).  The stored pieces
+// free: a wave's row maximum travels through LDS with the image it stores (per product 7 v_max3_i32 + 1 v_max_i32 over the wave's 16 values,
+// 6 DPP steps across the lanes, 1 v_max3_u32 + 1 v_max_u32 over the four waves' slots: ahf_wave_max).  The stored pieces
 // always stay below 2^15; the bound is loose by at most 2^6, i.e. entries down to 2^-12 of the largest keep full two-piece
 // precision and smaller ones an absolute error of 2^-34 of the largest (irrelevant: every entry is added to O(1) neighbours by
 // the back-projection).  The scales are powers of two (exact) and are undone once, in the epilogue factor.
 //
 // Layout, lane mapping, swapped-operand MFMA, transposing reads and the chunk rotation of the image are those of k_acyc_bf
-// (kernels_acyc_bf16.h); an image has two pieces (16 KiB), two images + the float staging rows of the epilogue 34 KiB per block:
-// four blocks per CU at 128 registers.
+// (kernels_acyc_bf16.h); an image has two pieces (16 KiB), two images + the float staging rows of the epilogue 34 KiB per block,
+// + the row maxima and a 256-byte zero page (34.3 KiB): four blocks per CU at 128 registers.
+// Vector instructions per wave and pair of chains at d = 50 (profiles/acyc_lean.txt): the draw loop carries the draw itself (62 Threefry,
+// 17 for the two uniforms and u / (u + (1 - u) e)) and two more (LDS address, the prefetched score's copy); the hand-over reads dwords
+// from a graph stored linearly in e and masks one tile; M = I + G~/d tests the diagonal in the wave's own tile only.
 // Measured and dropped: skipping the seven products of a chain whose soft graph is saturated everywhere (g (1 - g) = 0 on all edges, the
 // contribution is exactly zero) -- a flag per chain from the draw loop costs 2-3 us per launch and never fires: at t = 100 ... 1 000 of the
 // headline trajectory every chain keeps live edges (74.9 us per launch throughout, scripts/gpu_steady_bench.py).
@@ -35,7 +39,7 @@ typedef _Float16 ahf_f16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int AHF_NT = 4, AHF_TILE_BYTES = 64 * 32, AHF_PIECE_BYTES = AHF_NT * AHF_TILE_BYTES, AHF_IMG_BYTES = 2 * AHF_PIECE_BYTES,
               AHF_LDT = 68, AHF_IMG_STRIDE = 64 * AHF_LDT * 4 /* the float staging area of the epilogue overlays one image */,
-              AHF_LDS_BYTES = 2 * AHF_IMG_STRIDE + 64;
+              AHF_LDS_BYTES = 2 * AHF_IMG_STRIDE + 64 + 256 /* row maxima; zero page */;
 constexpr int AHF_E0 = 14;  // M = I + G~/d is stored as M 2^14 (largest entry exactly 1)
 
 // (x0, x1) s -> packed f16 pairs h, m with x s = h + m up to 2^-23 relative (s: a power of two, wave-uniform).  Four instructions per
@@ -180,15 +184,18 @@ __device__ __forceinline__ void ahf_matmul(f32x4 (&acc)[AHF_NT], const AhfFrag& 
 // largest of the wave's 16 x 64 accumulator values (all >= 0: bit patterns compare as integers), in every lane's SGPR copy
 template <int NT>
 __device__ __forceinline__ uint32_t ahf_wave_max(const f32x4 (&acc)[NT]) {
-  int v = 0;  // (integer maxima: fmaxf would canonicalise every input -- 24 extra instructions per product)
+  // (integer maxima: fmaxf would canonicalise every input -- 24 extra instructions per product)
+  // two values per instruction: one chain of max(max(x, y), v), which selects v_max3_i32 (a balanced tree of the 4 NT values does not)
+  int v = (int)__float_as_uint(acc[0][0]);
 #pragma unroll
-  for (int tj = 0; tj < NT; ++tj) {
-    const int x0 = (int)__float_as_uint(acc[tj][0]), x1 = (int)__float_as_uint(acc[tj][1]), x2 = (int)__float_as_uint(acc[tj][2]),
-              x3 = (int)__float_as_uint(acc[tj][3]);
-    const int t = x0 > x1 ? x0 : x1;
+  for (int j = 1; j + 1 < 4 * NT; j += 2) {
+    const int x = (int)__float_as_uint(acc[j >> 2][j & 3]), y = (int)__float_as_uint(acc[(j + 1) >> 2][(j + 1) & 3]);
+    const int t = x > y ? x : y;
     v = t > v ? t : v;
-    const int u = x2 > x3 ? x2 : x3;
-    v = u > v ? u : v;
+  }
+  {
+    const int x = (int)__float_as_uint(acc[NT - 1][3]);
+    v = x > v ? x : v;
   }
 #define AHF_DPP_MAX(ctrl, rmask)                                                     \
   {                                                                                  \
@@ -206,6 +213,41 @@ __device__ __forceinline__ uint32_t ahf_wave_max(const f32x4 (&acc)[NT]) {
 }
 __device__ __forceinline__ float ahf_pow2(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }
 
+// rng_uniform(bits, lo, 1) of two words at once, in packed operations, with the final max(v, lo) as ONE v_max_f32 per value
+// (rng_uniform: compare + select).  v and lo are positive, never NaN and lo is a normal number: the bits are those of the select.
+// (by inline assembly: fmaxf canonicalises lo first, inside the loop)
+__device__ __forceinline__ abf_f32x2 ahf_uniform2(uint32_t y0, uint32_t y1, float lo) {
+  const abf_f32x2 f = abf_f32x2{__uint_as_float((y0 >> 9) | 0x3F800000u), __uint_as_float((y1 >> 9) | 0x3F800000u)} - 1.0f;
+  const abf_f32x2 v = f * (1.0f - lo) + lo;  // (contracted, as rng_uniform's two calls are in this translation unit)
+  abf_f32x2 u;
+  asm("v_max_f32 %0, %1, %2" : "=v"(u.x) : "v"(v.x), "v"(lo));
+  asm("v_max_f32 %0, %1, %2" : "=v"(u.y) : "v"(v.y), "v"(lo));
+  return u;
+}
+// M = I + G~/d in the owner-lane layout.  Row a = 16 wave + r meets the diagonal only in column tile `wave` (wave-uniform), in the lane
+// group g4 = r >> 2, element r & 3: dg[i] says "element i of that tile is the diagonal of a row inside the matrix"; everything else is
+// a plain product (g is 0 outside the matrix and on the diagonal).  own[tj]: "tile tj is this wave's" as four independent flags (ahf_own):
+// four skippable blocks of four selects in place; written as tj == wave the compiler builds a switch that copies the other tiles
+__device__ __forceinline__ void ahf_own(int wave, int (&own)[AHF_NT]) {
+#pragma unroll
+  for (int tj = 0; tj < AHF_NT; ++tj) {
+    int f = __builtin_amdgcn_readfirstlane(wave == tj ? 1 : 0);
+    asm volatile("" : "+s"(f));
+    own[tj] = f;
+  }
+}
+__device__ __forceinline__ void ahf_m0(const f32x4 (&g)[AHF_NT], f32x4 (&v)[AHF_NT], const int (&own)[AHF_NT], const bool (&dg)[4], float inv_d) {
+#pragma unroll
+  for (int tj = 0; tj < AHF_NT; ++tj) v[tj] = g[tj] * inv_d;
+#pragma unroll
+  for (int tj = 0; tj < AHF_NT; ++tj)
+    if (own[tj]) {
+      asm volatile("; diagonal tile");  // (keeps the four selects inside the branch: folded, they are applied to all four tiles)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[tj][i] = dg[i] ? 1.0f : v[tj][i];
+    }
+}
+
 // FOUR: d > 48 (all four row / column tiles in use); the d <= 48 instantiation skips the fourth wave's products and the fourth column tile
 template <bool FOUR, int WPE>
 __device__ __forceinline__ void acyc_hf_block(const float* __restrict__ scores, const float* __restrict__ eas, float* __restrict__ part, Key2 carry, int m0,
@@ -214,16 +256,23 @@ __device__ __forceinline__ void acyc_hf_block(const float* __restrict__ scores, 
   extern __shared__ __attribute__((aligned(16))) float smem[];
   unsigned char* const sb = reinterpret_cast<unsigned char*>(smem);
   uint32_t* const slots = reinterpret_cast<uint32_t*>(sb + 2 * AHF_IMG_STRIDE);  // [2][4] row maxima of the waves, ping-pong
+  float* const zpage = reinterpret_cast<float*>(sb + 2 * AHF_IMG_STRIDE + 64);     // [64] zeros: what the lanes of rows >= d read as their graph
   // XCD-aware block order: all blocks of a particle on one XCD (see k_acyc_bf)
   const int L = blockIdx.x + gridDim.x * blockIdx.y, p_lo = L & 7, tq = L >> 3;
   const int bx = tq % (int)gridDim.x, m = (tq / (int)gridDim.x) * 8 + p_lo;
   if (m >= Mloc) return;  // (block-uniform)
-  const int blk = bx, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int blk = bx, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g4 = lane >> 4, r = lane & 15;
   const int a = 16 * wave + r, b0 = 4 * g4;  // row; first column within a tile
   const Key2 km = rng_split_row_uniform(carry, (uint32_t)M_global + 1u, (uint32_t)(m0 + m) + 1u, layout);  // dibs.py:595: key used directly
   const uint64_t dd = (uint64_t)d * d, nbits = (uint64_t)Sa * dd;
   const float inv_d = 1.0f / (float)d;
+  bool dg[4];  // element i of column tile `wave` is the diagonal of this lane's row (ahf_m0)
+#pragma unroll
+  for (int i = 0; i < 4; ++i) dg[i] = b0 + i == r && a < d;
+  int own[AHF_NT];
+  ahf_own(wave, own);
+  if (tid < 64) zpage[tid] = 0.f;  // (read after the barrier that ends the first draw phase)
   const bool fast = tau == 1.0f && eas != nullptr;  // sigmoid(eps + a) with eps = log(u / (1 - u))  ==  u / (u + (1 - u) exp(-a))
   const float* sm = (fast ? eas : scores) + (size_t)m * dd;  // fast: exp(-alpha s) from k_edge_scores (the same for every chain of the particle)
   const float ulo = tiny ? 1.17549435e-38f : 1.1920929e-07f;
@@ -248,66 +297,102 @@ __device__ __forceinline__ void acyc_hf_block(const float* __restrict__ scores, 
     // Soft graphs of BOTH chains of the pair, drawn in ELEMENT order -- thread tid takes elements e = tid, tid + 256, ... of the d x d
     // matrix: every lane busy (10 wave-draws per wave at d = 50 where the owner-lane order needs 14, the fourth wave's and the fourth
     // column tile's mostly for idle lanes), the Threefry counter is base + e, the score loads are coalesced and requested together --
-    // and handed to the owning lanes through LDS: G0 / G1 [64][AHF_LDT] float over the (free) images.
+    // and handed to the owning lanes through LDS: G0 / G1 [d d] float, LINEAR in e, over the (free) images.  The loop carries nothing
+    // per element but the draw itself: the index is tid + 256 k with k wave-uniform, so the score address advances on the scalar
+    // unit and the LDS address by a constant; the diagonal is drawn like any other element and cleared by its owner lane below
+    // (M ignores it, the back-projection needs g = 0 there); the last, partial iteration is peeled, the full ones test no bounds.
     {
       const int sa = unit;
       float* const G0 = reinterpret_cast<float*>(sb);
       float* const G1 = reinterpret_cast<float*>(sb + AHF_IMG_STRIDE);
-      const int ndd = (int)dd, ndraw = (ndd + 255) >> 8;
-      // (a, b) of element tid, advanced by 256 = qa d + qb per draw
-      const int qa = 256 / d, qb = 256 - qa * d;
-      int ea_ = tid / d, eb_ = tid - ea_ * d;
-      float s_next = tid < ndd ? sm[tid] : 0.f;  // (the next draw's score is requested one draw ahead)
+      const int ndd = (int)dd;
       const uint32_t cbase = (uint32_t)((uint64_t)sa * dd), chalf = (uint32_t)(nbits >> 1);
-      for (int k = 0; k < ndraw; ++k) {
-        const int e = tid + 256 * k;
-        const float s_cur = s_next;
-        s_next = e + 256 < ndd ? sm[e + 256] : 0.f;
-        if (e < ndd) {
-          float gv0 = 0.f, gv1 = 0.f;
-          if (ea_ != eb_) {
-            const float ea = fast ? s_cur : alpha * s_cur;
-            uint32_t y0, y1;
-            threefry2x32_uh(tk, (uint32_t)tid, cbase + 256u * (uint32_t)k, chalf, y0, y1);  // counter cbase + e: only tid is the lane's
-            if (fast) {
-              const float u0 = rng_uniform(y0, ulo, 1.0f), u1 = rng_uniform(y1, ulo, 1.0f);
-              // (saturated edges must give exactly 1 as the reference's sigmoid does: see k_acyc_bf)
-              const float den0 = fmaf(1.0f - u0, ea, u0), den1 = fmaf(1.0f - u1, ea, u1);
-              gv0 = den0 == u0 ? 1.0f : u0 * __builtin_amdgcn_rcpf(den0);
-              gv1 = den1 == u1 ? 1.0f : u1 * __builtin_amdgcn_rcpf(den1);
-            } else {
-              gv0 = 1.0f / (1.0f + expf(-tau * (rng_logistic(y0, tiny) + ea)));
-              gv1 = 1.0f / (1.0f + expf(-tau * (rng_logistic(y1, tiny) + ea)));
-            }
-          }
-          G0[ea_ * AHF_LDT + eb_] = gv0;
-          G1[ea_ * AHF_LDT + eb_] = gv1;
+      if (fast) {
+        const int nfull = ndd >> 8, rem = ndd & 255;  // (d >= 33: nfull >= 4)
+        const bool in_rem = tid < rem;
+        // scores through a buffer descriptor: lane offset 4 tid, the iteration's offset in an SGPR (no per-lane 64-bit address)
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sm), 0, 4 * ndd, 0x00020000);
+        const uint32_t voff = 4u * (uint32_t)tid;
+        uint32_t soff = 0u, off = cbase;
+        float* gp = G0 + tid;
+        const auto draw = [&](float ea) {
+          uint32_t y0, y1;
+          threefry2x32_uh(tk, (uint32_t)tid, off, chalf, y0, y1);  // counter cbase + e: only tid is the lane's
+          const abf_f32x2 u = ahf_uniform2(y0, y1, ulo);
+          // (saturated edges must give exactly 1 as the reference's sigmoid does: see k_acyc_bf)
+          const abf_f32x2 den = __builtin_elementwise_fma(1.0f - u, abf_f32x2{ea, ea}, u);
+          const abf_f32x2 q = u * abf_f32x2{__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
+          gp[0] = den.x == u.x ? 1.0f : q.x;
+          gp[AHF_IMG_STRIDE / 4] = den.y == u.y ? 1.0f : q.y;
+        };
+        float s_next = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, soff, 0));  // (requested one draw ahead)
+        for (int k = 0; k < nfull - 1; ++k) {
+          const float s_cur = s_next;
+          soff += 1024u;
+          s_next = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, soff, 0));
+          draw(s_cur);
+          off += 256u;
+          gp += 256;
         }
-        ea_ += qa;
-        eb_ += qb;
-        if (eb_ >= d) {
-          eb_ -= d;
-          ++ea_;
+        const float s_cur = s_next;
+        if (in_rem) s_next = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, soff + 1024u, 0));
+        draw(s_cur);  // the last full iteration
+        if (in_rem) {
+          off += 256u;
+          gp += 256;
+          draw(s_next);
+        }
+      } else {
+        for (int k = 0; 256 * k < ndd; ++k) {
+          const int e = tid + 256 * k;
+          if (e < ndd) {
+            const float ea = alpha * sm[e];
+            uint32_t y0, y1;
+            threefry2x32_uh(tk, (uint32_t)tid, cbase + 256u * (uint32_t)k, chalf, y0, y1);
+            G0[e] = 1.0f / (1.0f + expf(-tau * (rng_logistic(y0, tiny) + ea)));
+            G1[e] = 1.0f / (1.0f + expf(-tau * (rng_logistic(y1, tiny) + ea)));
+          }
         }
       }
       __syncthreads();
+      // owner lanes: row a, columns 16 tj + b0 .. + 3.  Rows are 4-byte aligned only (odd d): dword reads.  Lanes of rows beyond the
+      // matrix read the zero page.  Only the tile that holds column d - 1 (a constant of the instantiation) has columns to mask:
+      // they hold the next row's elements.
+      {
+        const float* const r0 = a < d ? G0 + a * d + b0 : zpage;
+        const float* const r1 = a < d ? G1 + a * d + b0 : zpage;
+        constexpr int TL = FOUR ? 3 : 2;
 #pragma unroll
-      for (int tj = 0; tj < AHF_NT; ++tj) {
-        f32x4 v0 = f32x4{0.f, 0.f, 0.f, 0.f}, v1 = v0;
-        if (a < d && (FOUR || tj < 3)) {
-          v0 = *reinterpret_cast<const f32x4*>(G0 + a * AHF_LDT + 16 * tj + b0);
-          v1 = *reinterpret_cast<const f32x4*>(G1 + a * AHF_LDT + 16 * tj + b0);
-          if (16 * tj + 16 > d) {  // (wave-uniform: the tile that holds column d - 1; columns beyond hold stale LDS)
+        for (int tj = 0; tj < AHF_NT; ++tj) {
+          f32x4 v0 = f32x4{0.f, 0.f, 0.f, 0.f}, v1 = v0;
+          if (tj <= TL) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-              const bool in = b0 + 16 * tj + i < d;
-              v0[i] = in ? v0[i] : 0.f;
-              v1[i] = in ? v1[i] : 0.f;
+              v0[i] = r0[16 * tj + i];
+              v1[i] = r1[16 * tj + i];
+            }
+            if (tj == TL) {
+#pragma unroll
+              for (int i = 0; i < 4; ++i) {
+                const bool in = b0 + 16 * TL + i < d;
+                v0[i] = in ? v0[i] : 0.f;
+                v1[i] = in ? v1[i] : 0.f;
+              }
             }
           }
+          g[tj] = v0;
+          gnext[tj] = v1;
         }
-        g[tj] = v0;
-        gnext[tj] = v1;
+#pragma unroll
+        for (int tj = 0; tj < AHF_NT; ++tj)
+          if (own[tj]) {
+            asm volatile("; diagonal tile");  // (see ahf_m0)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              g[tj][i] = dg[i] ? 0.f : g[tj][i];
+              gnext[tj][i] = dg[i] ? 0.f : gnext[tj][i];
+            }
+          }
       }
       __syncthreads();  // the images are written next
     }
@@ -318,7 +403,7 @@ __device__ __forceinline__ void acyc_hf_block(const float* __restrict__ scores, 
       }
       AhfFrag A;
       f32x4 acc[AHF_NT];
-      abf_m0(g, acc, a, b0, d, inv_d);
+      ahf_m0(g, acc, own, dg, inv_d);
       ahf_make_frag(acc, s0, A);
       AhfFrag AM;               // M's own fragments for the "times M" steps (kept when the register budget allows: WPE == 3)
       if constexpr (WPE <= 3) AM = A;
@@ -362,7 +447,7 @@ __device__ __forceinline__ void acyc_hf_block(const float* __restrict__ scores, 
             } else {
               f32x4 mv[AHF_NT];
               AhfFrag A0;
-              abf_m0(g, mv, a, b0, d, inv_d);
+              ahf_m0(g, mv, own, dg, inv_d);
               ahf_make_frag(mv, s0, A0);
               if (row_active) ahf_matmul<FOUR>(acc, A0, sb + cur, rd_off);
             }
