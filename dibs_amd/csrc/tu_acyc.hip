@@ -32,7 +32,8 @@ static void launch_nt(const AcycLaunch& a) {
 static bool acyc_use_bf16(const AcycLaunch& a) { return a.pipe != DIBS_PIPE_F32 && a.units != a.Sa && a.d >= 33 && a.d <= 64; }
 // 65 <= d <= 112 with paired chains: the same schemes with NT = 5 .. 7 tiles and waves (k_acyc_hfw / k_acyc_bfw)
 static bool acyc_use_bfw(const AcycLaunch& a) { return a.pipe != DIBS_PIPE_F32 && a.units != a.Sa && a.d > 64 && a.d <= 112; }
-// two-piece f16 operands for 65 <= d <= 112 (k_acyc_hfw, kernels_acyc_f16.h); DIBS_ACYC_BF16=1 keeps k_acyc_bfw (A/B runs)
+// two-piece f16 operands for 65 <= d <= 112 (k_acyc_hfw, kernels_acyc_f16.h): the default of the whole range.  k_acyc_bfw runs only with
+// DIBS_ACYC_BF16=1 (A/B runs) or above a.hfw_max (DIBS_ACYC_HFW_MAX, default 112: nowhere; tests/hparam_states.py sets 80 to reach it)
 template <int NT>
 static void launch_hfw(const AcycLaunch& a) {
   const size_t lds = ahfw_lds_bytes(NT);

@@ -136,6 +136,10 @@ SIGNAL_SHARE = dict(z=0.95, theta=0.75)   # (the float64 oracle has 0.965 .. 0.9
 
 
 # ---- the cases ------------------------------------------------------------------------------------------------------------------------------
+SCALED = dict(scale_latent=0.5)                        # the `_scaled` rows: make_config's scale_latent / scale_theta off their default 1
+SCALED_JOINT = dict(scale_latent=0.5, scale_theta=3.0)
+
+
 def _case(name, family, d, M, state, *, t=0, k=None, S=4, Sa=2, N=20, optimizer="rmsprop", env=None, exempt=(), **model_kw):
     """name: the branch the case exists for.  family: marginal | lingauss | densenn.  state: wide | neighbours | offset_cluster | far.
     t = 0: the repulsion regime (prior gradient only); t > 0: the gradient regime.  env: tuning switches set before the engine is created.
@@ -187,6 +191,10 @@ def _joint_rows():
         rows.append(_case(f"gemm_joint_d5_M{M}_{s}", "lingauss", 5, M, s, t=t, **lin))
     rows += [_case("gemm_joint_d6_M256_neighbours", "lingauss", 6, 256, "neighbours", **lin),
              _case("gemm_joint_d6_M319_wide", "lingauss", 6, 319, "wide", t=2, optimizer="gd", **lin)]
+    # the kernel scales off 1 (K = scale exp(-|.|^2 / h): the weights of phi's drive AND of its repulsion): k_phi_update<4, *, true> with the
+    # direct kernel matrix, and k_phi_gemm<true> at M = 256
+    rows += [_case("phi4_joint_lin_d6_M33_scaled", "lingauss", 6, 33, "neighbours", **lin, **SCALED_JOINT),
+             _case("gemm_joint_d6_M256_scaled", "lingauss", 6, 256, "neighbours", **lin, **SCALED_JOINT)]
     return rows
 
 
@@ -219,6 +227,14 @@ def _kmat_rows():
         _case("kmat_tile64_M65", "marginal", 6, 65, "wide", env=dict(alone, DIBS_KMAT_T64_MIN="64", **TILED(64))),
         _case("kmat_tile64_far_M130", "marginal", 50, 130, "far", S=2, N=60, env=dict(alone, DIBS_KMAT_T64_MIN="64"),
               exempt=("weights", "cross", "repulsion")),
+        # scale_latent = 0.5 (joint: and scale_theta = 3) on each of the places above: direct, in k_bge_sample, tiled with k_kmat_finish,
+        # in-tail riders, second stream tiled, 64 x 64 tiles (k_phi_gemm at M = 256: _joint_rows)
+        _case("kmat_direct_scaled_M33", "marginal", 6, 33, "wide", env=alone, **SCALED),
+        _case("kmat_insample_scaled_M65", "marginal", 6, 65, "neighbours", S=40, **SCALED),
+        _case("kmat_tiled_split_finish_scaled_M33_D5000", "marginal", 50, 33, "neighbours", S=2, N=60, env=dict(alone, **TILED(32)), **SCALED),
+        _case("kmat_intail_scaled_M130_D288", "marginal", 12, 130, "wide", S=72, N=40, **SCALED),
+        _case("kmat_stream2_tiled_scaled_M130", "lingauss", 5, 130, "neighbours", grad_estimator_z="reparam", **SCALED_JOINT),
+        _case("kmat_tile64_scaled_M65", "marginal", 6, 65, "wide", env=dict(alone, DIBS_KMAT_T64_MIN="64", **TILED(64)), **SCALED),
     ]
 
 
