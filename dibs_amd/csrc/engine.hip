@@ -517,24 +517,35 @@ static bool same_derived(const ProblemHP& a, const ProblemHP& b) {
          a.inv_sig2 == b.inv_sig2 && a.h == b.h && a.stepsize == b.stepsize && a.h_theta == b.h_theta;
 }
 
+// what the per-problem and the per-chain accessors check alike, each with its own wording: the run index (`range`); for a setter
+// (set != null) also that the table is not final yet (`frozen`) and the edge probability of an Erdos-Renyi prior (`er`)
+static int hp_check(const dibs_engine* e, int i, const std::string& range, const dibs_chain_hparams* set = nullptr, const std::string& frozen = "",
+                    const std::string& er = "") {
+  if (i < 0 || i >= e->B) return fail(range);
+  if (!set) return 0;
+  if (e->hp_final) return fail(frozen);
+  const dibs_config c = problem_config(e, *set);
+  if (c.graph_prior == DIBS_PRIOR_ER) {  // (what dibs_engine_create asks of the shared value)
+    const double pr = er_edge_prob(c);
+    if (!(pr > 0.0 && pr < 1.0)) return fail(er + ": Erdos-Renyi prior: edge probability must be in (0, 1)");
+  }
+  return 0;
+}
+
 extern "C" int dibs_engine_set_problem_hparams(dibs_engine* e, int32_t p, const dibs_problem_hparams* hp) {
   if (!e || !hp) return fail("batched engine: dibs_engine_set_problem_hparams: null engine or argument");
   if (refuse_chains(e, "dibs_engine_set_problem_hparams (the chains of a JointDiBS + LinearGaussian engine take their own values through "
                        "dibs_engine_set_chain_hparams)"))
     return 1;
   if (e->B <= 1) return fail("batched engine: dibs_engine_set_problem_hparams needs one (dibs_config.reserved_i[0] = n_problems must be > 1)");
-  if (p < 0 || p >= e->B) return fail("batched engine: dibs_engine_set_problem_hparams: problem index out of range");
-  if (e->hp_final)
-    return fail("batched engine: dibs_engine_set_problem_hparams after the particles were initialised (init_particles_batch / set_state / run): "
-                "latent_prior_std enters the initial draw and the device table is written once");
   // (h_theta: a marginal model has no parameter kernel; the configuration's value rides along)
   const dibs_chain_hparams h{hp->alpha_linear, hp->beta_linear, hp->h_latent, e->cfg.h_theta, hp->stepsize, hp->score_function_baseline,
                              hp->latent_prior_std, hp->graph_prior_edges_per_node};
-  const dibs_config c = problem_config(e, h);
-  if (c.graph_prior == DIBS_PRIOR_ER) {  // (what dibs_engine_create asks of the shared value)
-    const double pr = er_edge_prob(c);
-    if (!(pr > 0.0 && pr < 1.0)) return fail("batched engine: problem " + std::to_string(p) + ": Erdos-Renyi prior: edge probability must be in (0, 1)");
-  }
+  if (hp_check(e, p, "batched engine: dibs_engine_set_problem_hparams: problem index out of range", &h,
+               "batched engine: dibs_engine_set_problem_hparams after the particles were initialised (init_particles_batch / set_state / run): "
+               "latent_prior_std enters the initial draw and the device table is written once",
+               "batched engine: problem " + std::to_string(p)))
+    return 1;
   if (!e->hp_tier && !same_derived(derive_problem_hp(e, h), derive_problem_hp(e, config_hparams(e->cfg))))
     return fail("batched engine: problem " + std::to_string(p) + ": hyper-parameters that differ from the configuration's need n_vars <= 64 and "
                 "n_dim <= 64 (and the default acyclicity pipe); this engine's kernels take them as launch arguments of the whole batch");
@@ -545,7 +556,7 @@ extern "C" int dibs_engine_set_problem_hparams(dibs_engine* e, int32_t p, const 
 extern "C" int dibs_engine_get_problem_hparams(dibs_engine* e, int32_t p, dibs_problem_hparams* hp) {
   if (!e || !hp) return fail("batched engine: dibs_engine_get_problem_hparams: null engine or argument");
   if (e->B <= 1) return fail("batched engine: dibs_engine_get_problem_hparams needs one (dibs_config.reserved_i[0] = n_problems must be > 1)");
-  if (p < 0 || p >= e->B) return fail("batched engine: dibs_engine_get_problem_hparams: problem index out of range");
+  if (hp_check(e, p, "batched engine: dibs_engine_get_problem_hparams: problem index out of range")) return 1;
   const dibs_chain_hparams& h = e->hp_host[(size_t)p];
   *hp = dibs_problem_hparams{h.alpha_linear, h.beta_linear, h.h_latent, h.stepsize, h.score_function_baseline, h.latent_prior_std,
                              h.graph_prior_edges_per_node};
@@ -567,15 +578,11 @@ extern "C" int dibs_engine_set_chain_hparams(dibs_engine* e, int32_t c, const di
   const std::string pre = "chains engine (n_chains > 1): dibs_engine_set_chain_hparams: ";
   if (!e || !hp) return fail(pre + "null engine or argument");
   if (!e->chains) return fail(pre + "needs a chains engine (dibs_config.reserved_i[2] = n_chains must be > 1)");
-  if (c < 0 || c >= e->B) return fail(pre + "chain index " + std::to_string(c) + " out of range (n_chains = " + std::to_string(e->B) + ")");
-  if (e->hp_final)
-    return fail(pre + "called after the particles were initialised (init_particles_batch / set_state / run): latent_prior_std enters the "
-                      "initial draw and the device table is written once");
-  const dibs_config cc = problem_config(e, *hp);
-  if (cc.graph_prior == DIBS_PRIOR_ER) {  // (what dibs_engine_create asks of the shared value)
-    const double pr = er_edge_prob(cc);
-    if (!(pr > 0.0 && pr < 1.0)) return fail(pre + "chain " + std::to_string(c) + ": Erdos-Renyi prior: edge probability must be in (0, 1)");
-  }
+  if (hp_check(e, c, pre + "chain index " + std::to_string(c) + " out of range (n_chains = " + std::to_string(e->B) + ")", hp,
+               pre + "called after the particles were initialised (init_particles_batch / set_state / run): latent_prior_std enters the "
+                     "initial draw and the device table is written once",
+               pre + "chain " + std::to_string(c)))
+    return 1;
   if (differs_from_config(e, *hp)) {
     if (e->cfg.likelihood != DIBS_LIK_LINGAUSS)
       return fail(pre + "chain " + std::to_string(c) + ": hyper-parameters that differ from the configuration's are LinearGaussian only (the "
@@ -596,7 +603,7 @@ extern "C" int dibs_engine_get_chain_hparams(dibs_engine* e, int32_t c, dibs_cha
   const std::string pre = "chains engine (n_chains > 1): dibs_engine_get_chain_hparams: ";
   if (!e || !hp) return fail(pre + "null engine or argument");
   if (!e->chains) return fail(pre + "needs a chains engine (dibs_config.reserved_i[2] = n_chains must be > 1)");
-  if (c < 0 || c >= e->B) return fail(pre + "chain index " + std::to_string(c) + " out of range (n_chains = " + std::to_string(e->B) + ")");
+  if (hp_check(e, c, pre + "chain index " + std::to_string(c) + " out of range (n_chains = " + std::to_string(e->B) + ")")) return 1;
   *hp = e->hp_host[(size_t)c];
   return 0;
 }
@@ -651,7 +658,7 @@ int batch_hp_commit(dibs_engine* e) {
   HIP_OK(hipMemcpy(e->hp, tab.data(), tab.size() * sizeof(ProblemHP), hipMemcpyHostToDevice));
   e->hp_final = true;
   if (e->chains) {
-    // the chains' tier: some chain's scalars differ from the configuration's -- step_chains takes the table-reading launches.  The
+    // the chains' tier: some chain's scalars differ from the configuration's -- step_multi takes the table-reading launches.  The
     // per-chain forms of the LinearGaussian kernels (per-chain data) read alpha and the baseline rate from the table either way
     e->hp_tier = chains_hp_differ(e);
     e->jw.chain_hp = e->hp;
@@ -751,15 +758,10 @@ extern "C" int dibs_engine_run(dibs_engine* e, int32_t t_start, int32_t n_steps)
                 "(dibs_engine_set_chain_hparams), which needs per-chain data: dibs_engine_set_data_problem has not been called for every chain");
   if (!e->has_data) return fail("dibs_engine_set_data has not been called");
   if (need_edge_prior(e)) return 1;
-  if (e->chains) {
+  if (e->B > 1) {  // (batched or chains engine)
     HIP_OK(hipSetDevice(e->cfg.device_id));
     if (batch_hp_commit(e)) return 1;
-    return run_chunk(e, t_start, n_steps, [e](int t) { return step_chains(e, t); });
-  }
-  if (e->B > 1) {
-    HIP_OK(hipSetDevice(e->cfg.device_id));
-    if (batch_hp_commit(e)) return 1;
-    return run_chunk(e, t_start, n_steps, [e](int t) { return step_batch(e, t); });
+    return run_chunk(e, t_start, n_steps, [e](int t) { return step_multi(e, t); });
   }
   if (e->f64) {
     HIP_OK(hipSetDevice(e->cfg.device_id));

@@ -87,7 +87,7 @@ int f64_init_particles(dibs_engine* e, Key2 isub) {
 
 // ---- float64 engine (dibs_config.reserved_i[1] = 64, include/dibs_hip.h; kernels_f64.h) ----------------------------------------------
 // One step: the loop-carry key advances as in step_local (split for the likelihood, then for the prior); edge scores on the main stream,
-// the acyclicity chains, their reduction and the kernel matrix on the second stream (fork / join by events: EventFork, as step_batch), BGe sampling and
+// the acyclicity chains, their reduction and the kernel matrix on the second stream (fork / join by events: EventFork, as step_multi), BGe sampling and
 // node scores -> weights -> per-particle gradient -> phi -> optimizer on the main stream.
 int step_f64(dibs_engine* e, int t) {
   const dibs_config& c = e->cfg;

@@ -80,12 +80,12 @@ struct dibs_engine {
   int d, k, M, Mloc, m0, N, S, Sa, W;
   // batched engine (cfg.reserved_i[0] = n_problems = B > 1): B independent problems of M particles each; the device arrays hold Mloc = B * M
   // rows, problem-major (m0 = 0).  M stays the size of ONE problem, so every choice the standalone engine makes from its particle count
-  // (acyclicity chain grouping, kernel-matrix algorithm) is made the same way here.  See step_batch.
+  // (acyclicity chain grouping, kernel-matrix algorithm) is made the same way here.  See step_multi.
   int B = 1;
   Key2* bcarry = nullptr;                             // [B] loop-carry keys, advanced on the device (k_batch_keys)
   Key2 *bkeys_lik = nullptr, *bkeys_prior = nullptr;  // [B * M] this step's per-particle keys
   // chains engine (cfg.reserved_i[2] = n_chains = C > 1): C chains of ONE joint model on ONE data set.  B = C and the rows are laid out as
-  // a batched engine's (chain-major, M = one chain's particles); every hyper-parameter is shared, and so is the data ...  See step_chains.
+  // a batched engine's (chain-major, M = one chain's particles); every hyper-parameter is shared, and so is the data ...  See step_multi.
   bool chains = false;
   Key2* bkeys_theta = nullptr;                        // [C * M] this step's keys of the theta estimator (k_chain_keys)
   // ... or, LinearGaussian only, every chain on a data set of its own (dibs_engine_set_data_problem for every chain; engine_data.hip): the
@@ -101,7 +101,7 @@ struct dibs_engine {
   // batch-only kernels do (kernel matrix, phi, keys) and the rest take the configuration's values as launch arguments, as before
   // Chains engines keep the same host values and the same table per CHAIN (dibs_engine_set_chain_hparams: h_theta as well, which a batched
   // engine leaves at the configuration's).  chain_hp_ok: the condition of hp_tier for a chains engine, what differing values need;
-  // hp_tier of a chains engine is decided by batch_hp_commit: some chain's derived values differ from the configuration's (step_chains then
+  // hp_tier of a chains engine is decided by batch_hp_commit: some chain's derived values differ from the configuration's (step_multi then
   // takes the table-reading launches, otherwise it is launch for launch what it always was).
   std::vector<dibs_chain_hparams> hp_host;
   ProblemHP* hp = nullptr;  // [B]
@@ -288,7 +288,7 @@ struct DevBuf {
   hipError_t alloc(size_t n) { return dalloc(&p, n); }
 };
 
-// Fork / join of the second stream by events, as step_batch and step_f64 do it (step_local has its own: ForkKind / JoinKind, step_plan.h):
+// Fork / join of the second stream by events, as step_multi and step_f64 do it (step_local has its own: ForkKind / JoinKind, step_plan.h):
 //   fork() -- the second stream's chain on s2 -- chain_done() -- the main stream's chain -- join() -- the first reader of the chain's results.
 // Without a second stream s2 is the main stream and the calls do nothing; while per-kernel timing is on, chain_done() joins right away.
 struct EventFork {
@@ -360,18 +360,17 @@ int join_failure(unsigned int code, const char* what);
 // ---- engine_step.hip ----
 int step_local(dibs_engine* e, int t, const RowTarget& rt, const StepKeys* xk = nullptr, int terms = TERMS_ALL, const float* zero_w = nullptr);
 int step_update(dibs_engine* e, int t, const RowSource& rs, float* vals_send = nullptr);
-int step_batch(dibs_engine* e, int t);
-int step_chains(dibs_engine* e, int t);
+int step_multi(dibs_engine* e, int t);  // (one step of a batched or a chains engine)
 int carry_copy(dibs_engine* e, bool restore);
 void launch_stream_probe(hipStream_t main_stream, hipStream_t second_stream, unsigned int* words);  // k_probe_wait / k_probe_set (engine_alloc)
-// ---- tu_batch.hip: the table-reading launches of step_batch (n_vars, n_dim <= 64; dibs_engine::hp_tier) ----
+// ---- tu_batch.hip: the table-reading launches of step_multi (n_vars, n_dim <= 64; dibs_engine::hp_tier) ----
 void batch_launch_edge_scores(hipStream_t st, const float* z, float* scores, uint32_t* thr, float* probs, float* eas, const ProblemHP* hp, int pM,
                               int Mloc, int d, int k, int dpad, int ldk);
 void batch_launch_tail(hipStream_t st, const TailArgs& ta, const ProblemHP* hp, int pM, int Mloc, size_t lds);
 void batch_launch_acyc_power(const AcycLaunch& a, const ProblemHP* hp, int pM);
 // ---- tu_tail_edge.hip: k_particle_grad with the table of an edge-wise graph prior in place of the Erdos-Renyi constant ----
 void edge_launch_tail(hipStream_t st, const TailArgs& ta, const float* tab, int blocks, size_t lds);
-// ---- tu_batch.hip: the chain-aware launches of step_chains (keys, block-diagonal kernel matrices) ----
+// ---- tu_batch.hip: the chain-aware launches of step_multi (keys, block-diagonal kernel matrices) ----
 void chains_launch_keys(hipStream_t st, Key2* carry, Key2* keys_theta, Key2* keys_lik, Key2* keys_prior, int C, int M, int layout);
 void chains_launch_kmat(hipStream_t st, bool tiled, const float* x, size_t len, float* kout, int C, int M, float scale, float h, const float* kadd,
                         float* ksum, size_t lds_direct);

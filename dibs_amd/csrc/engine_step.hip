@@ -1,5 +1,5 @@
 // One SVGD step of the float32 engines (include/dibs_hip.h): the launch blocks, step_local / step_update (phases A and B, split at the
-// exchange point), step_batch, and the entry points that drive them.  The kernels of kernels_marginal.h and kernels_tail.h are compiled here,
+// exchange point), step_multi, and the entry points that drive them.  The kernels of kernels_marginal.h and kernels_tail.h are compiled here,
 // and only here.
 #define DIBS_TU_STEP
 #include "kernels_marginal.h"
@@ -588,17 +588,30 @@ int carry_copy(dibs_engine* e, bool restore) {
   return 0;
 }
 
-// ---- batched engine (n_problems = B > 1, include/dibs_hip.h) -------------------------------------------------------------------------
-// One step of B independent problems in the launches of one standalone step: rows [B * M] problem-major, every per-particle kernel over all
-// rows with explicit keys (Mg = -1, rng_explicit_row) that k_batch_keys derives from the B device-resident carries; the BGe kernels look up
-// problem m / M's statistics (BATCH instantiations); the kernel matrix is block-diagonal [B * M][M] and phi sums over a problem's own block.
-// Fork / join of the second stream by events only (no flags), the kernel matrix standalone on the second stream (no fusions).
-// Hyper-parameters: per problem, from the device table e->hp (ProblemHP; dibs_engine_set_problem_hparams, by default the configuration's
-// values in every row).  k_batch_keys forms this step's alpha and beta of every problem in double, as the host does for a standalone
-// engine; the kernel matrix and phi always read the table, the edge, acyclicity and tail kernels do where they have a table-reading form
-// (e->hp_tier) and otherwise take the configuration's values as launch arguments (set_problem_hparams accepts no others there).
-// The table-reading forms of the edge, acyclicity and tail launches (e->hp_tier; kernels and launchers in tu_batch.hip): launch blocks of
-// step_batch alone, so that the blocks the standalone step shares with it stay what they were.
+// ---- multi-run engines (include/dibs_hip.h): batched (n_problems = B > 1) and chains (n_chains = C > 1, e->chains, B = C) ----------------
+// One step of B runs in the launches of one standalone step: rows [B * M] run-major, every per-particle kernel over all rows with explicit
+// keys (Mg = -1, rng_explicit_row) that the keys kernel derives from the B device-resident carries; the kernel matrices are block-diagonal
+// [B * M][M] and phi sums over a run's own block (k_phi_update's BATCH forms, grid.y = run).  Fork / join of the second stream by events
+// only (no flags), the kernel matrices standalone on the second stream (no fusions).  Every choice a standalone engine makes from its
+// particle count is made from M, one run's (acyc_cpb, the kernel-matrix algorithm, phi's TA / FULL, JointLaunch::M_choice), never from B * M.
+// The two kinds differ where step_local branches between the BGe score estimator and a joint model:
+//  * batched: B independent MarginalDiBS + BGe problems, each with its own data.  The BGe kernels look up problem m / M's statistics (BATCH
+//    instantiations); one kernel matrix (latent).
+//  * chains: C chains of one joint model.  The data is shared, so every kernel that reads it runs unchanged over all rows; chain-aware are
+//    the keys, the two kernel matrices (latent -> kz, theta -> kt and kz + kt -> ksum) and phi (JOINT + BATCH forms).  With per-chain data
+//    (LinearGaussian, dibs_engine_set_data_problem for every chain) the step is the same: the launchers of tu_lin.hip take the per-chain
+//    forms of the data-reading kernels (tu_lin_chains.hip) when the workspace holds JointWork::n_chain_data data sets.
+// Hyper-parameters: per run, from the device table e->hp (ProblemHP; dibs_engine_set_problem_hparams / dibs_engine_set_chain_hparams, by
+// default the configuration's values in every row).  A batched engine's keys kernel forms this step's alpha and beta of every problem in
+// double, as the host does for a standalone engine; its kernel matrix and phi always read the table.  The edge, acyclicity and tail kernels
+// read it where they have a table-reading form (e->hp_tier; kernels and launchers in tu_batch.hip, pM = M) and otherwise take the
+// configuration's values as launch arguments (set_problem_hparams accepts no others there).  e->hp_tier of a chains engine: some chain's
+// values differ from the configuration's (LinearGaussian with per-chain data, n_vars, n_dim <= 64).  Then the keys launch also forms every
+// chain's alpha and beta in its row of the table, the kernel matrices take chain p's h / h_theta, phi reads the table as it always did, and
+// the per-chain estimator kernels take alpha and the baseline rate of the block's chain (LinChainData::hp; they always do).  Without
+// differing values the launches are those of a chains engine on which nothing was set.
+// The table-reading forms of the edge, acyclicity and tail launches are launch blocks of step_multi alone, so that the blocks the
+// standalone step shares with it stay what they were.
 static void batch_edge_scores(dibs_engine* e) {
   KTimer tm(e, DIBS_K_EDGE, e->stream);
   batch_launch_edge_scores(e->stream, e->z, e->scores, e->thr, e->probs, e->eas, e->hp, e->M, e->Mloc, e->d, e->k, e->dpad, e->ldk);
@@ -615,26 +628,30 @@ static void batch_acyc(dibs_engine* e, hipStream_t st, Key2 carry) {
   KTimer tm(e, DIBS_K_ACYC_REDUCE, st);
   acyc_launch_reduce(al);
 }
-// (BGe score estimator with the prior terms, W, U, V in LDS, no riders, no join flag: what step_batch asks of launch_tail)
-static void batch_tail(dibs_engine* e, const RowTarget& rt) {
+// (the tail as launch_tail builds it for a multi-run step -- score_lik: the BGe score estimator, otherwise a joint model; prior terms on,
+//  W, U, V in LDS, no riders, no join flag; alpha, beta, the prior constant, 1 / sigma^2 and the baseline rate: k_particle_grad_batch fills
+//  them in from the table)
+static void multi_tail_hp(dibs_engine* e, const RowTarget& rt, bool score_lik) {
   const dibs_config& c = e->cfg;
   KTimer tm(e, DIBS_K_TAIL);
-  const int ldz = tail_ldz(e->d, e->k, e->S, true, LDS_LIMIT - 2048);
-  const int cap = tail_stage_cap(e->d, ldz, e->S, e->W, LDS_LIMIT - 2048);
-  const size_t lds = tail_lds_bytes(e->d, ldz, e->S, e->W, true, cap);
-  // (alpha, beta, the prior constant, 1 / sigma^2 and the baseline rate: k_particle_grad_batch fills them in from the table)
-  const TailArgs ta{e->node_scores, e->masks, e->logprobs_z, e->baseline, e->baseline2, 0.0, e->bq.counts, e->S, e->W, cap, e->probs, e->w_lik,
-                    e->w_acyc, 0.f, 0.f, c.graph_prior, 0.f, e->z, rt.base, rt.stride, rt.copy_vals, 0, e->d, e->k, ldz, 0.f, nullptr, nullptr,
-                    nullptr, 0u, nullptr, e->Mloc,
+  const int ldz = tail_ldz(e->d, e->k, e->S, score_lik, LDS_LIMIT - 2048);
+  const int cap = score_lik ? tail_stage_cap(e->d, ldz, e->S, e->W, LDS_LIMIT - 2048) : 0;
+  const size_t lds = tail_lds_bytes(e->d, ldz, e->S, e->W, score_lik, cap);
+  const TailArgs ta{score_lik ? e->node_scores : nullptr, e->masks, e->logprobs_z, e->baseline, e->baseline2, 0.0,
+                    score_lik ? e->bq.counts : nullptr, e->S, e->W, cap, e->probs, e->w_lik, e->w_acyc, 0.f, 0.f, c.graph_prior, 0.f, e->z,
+                    rt.base, rt.stride, rt.copy_vals, 0, e->d, e->k, ldz, 0.f, nullptr, nullptr, nullptr, 0u, nullptr, e->Mloc,
                     KmatTile{nullptr, 0, 0, 0, nullptr, 0, 0, 0, 1, 0, 0, 0, 1, 1, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr}};
   batch_launch_tail(e->stream, ta, e->hp, e->M, e->Mloc, lds);
 }
 
+// the kernel-matrix algorithm of a standalone engine of M particles (its kmat_tiled_on): tiled from kmat_tiled_min particles, direct below
+static bool multi_kmat_tiled(const dibs_engine* e) {
+  return e->M >= e->tune.kmat_tiled_min && kmat_tile_addressable((size_t)2 * e->M, e->E > e->Ev ? e->E : e->Ev, 0, 0);
+}
 static void kmat_batch(dibs_engine* e, hipStream_t st) {
   const dibs_config& c = e->cfg;
   KTimer tm(e, DIBS_K_KMAT, st);
-  // the algorithm of a standalone engine of M particles (kmat_tiled_on): tiled from kmat_tiled_min particles, direct below
-  if (e->M >= e->tune.kmat_tiled_min && kmat_tile_addressable((size_t)2 * e->M, e->E > e->Ev ? e->E : e->Ev, 0, 0)) {
+  if (multi_kmat_tiled(e)) {
     const int nta = (e->M + KT_T - 1) / KT_T, tiles = kmat_tile_count(nta, nta, 1), nchunk = kmat_nchunk((int)e->D);
     const KmatTile kt{e->z, (size_t)e->D, 0, (int)e->D, nullptr, 0, e->M, e->M, nchunk, nta, nta, 1, 1, nchunk, (float)c.scale_latent,
                       (float)c.h_latent, e->kz, nullptr, nullptr, nullptr};
@@ -647,124 +664,76 @@ static void kmat_batch(dibs_engine* e, hipStream_t st) {
   hipLaunchKernelGGL(k_kmat_batch, dim3(e->Mloc, (e->M + KMAT_BT - 1) / KMAT_BT), dim3(256), lds, st, (const float*)e->z, (size_t)e->D, (int)e->D,
                      e->kz, e->M, (float)c.scale_latent, (const ProblemHP*)e->hp);
 }
-
-int step_batch(dibs_engine* e, int t) {
+static void kmat_chains(dibs_engine* e, hipStream_t st) {
   const dibs_config& c = e->cfg;
+  KTimer tm(e, DIBS_K_KMAT, st);
+  const bool tiled = multi_kmat_tiled(e);
+  if (e->hp_tier) {
+    chains_launch_kmat_hp(st, tiled, e->z, (size_t)e->D, e->kz, e->B, e->M, (float)c.scale_latent, e->hp, 0, nullptr, nullptr,
+                          kmat_lds_bytes((size_t)e->D));
+    chains_launch_kmat_hp(st, tiled, e->theta, (size_t)e->P, e->kt, e->B, e->M, (float)c.scale_theta, e->hp, 1, e->kz, e->ksum,
+                          kmat_lds_bytes((size_t)e->P));
+  } else {
+    chains_launch_kmat(st, tiled, e->z, (size_t)e->D, e->kz, e->B, e->M, (float)c.scale_latent, (float)c.h_latent, nullptr, nullptr,
+                       kmat_lds_bytes((size_t)e->D));
+    chains_launch_kmat(st, tiled, e->theta, (size_t)e->P, e->kt, e->B, e->M, (float)c.scale_theta, (float)c.h_theta, e->kz, e->ksum,
+                       kmat_lds_bytes((size_t)e->P));
+  }
+}
+
+int step_multi(dibs_engine* e, int t) {
+  const dibs_config& c = e->cfg;
+  const bool chains = e->chains, tier = e->hp_tier;
   const float alpha = (float)(c.alpha_linear * t), beta = (float)(c.beta_linear * t);
   const int L = c.rng_layout, R = e->Mloc;  // (one rank: m0 = 0)
-  hipLaunchKernelGGL(k_batch_keys, dim3(e->B), dim3(256), 0, e->stream, e->bcarry, e->bkeys_lik, e->bkeys_prior, e->M, L, e->hp, t);
+  if (!chains) {
+    hipLaunchKernelGGL(k_batch_keys, dim3(e->B), dim3(256), 0, e->stream, e->bcarry, e->bkeys_lik, e->bkeys_prior, e->M, L, e->hp, t);
+  } else if (tier || e->jw.n_chain_data) {
+    // (per-chain data: the per-chain estimator kernels read the step's alpha from the table, so the keys launch forms it there also when no
+    //  chain's values differ -- the same launch with two more stores per chain)
+    chains_launch_keys_hp(e->stream, e->bcarry, e->bkeys_theta, e->bkeys_lik, e->bkeys_prior, e->B, e->M, L, e->hp, t);
+  } else {
+    chains_launch_keys(e->stream, e->bcarry, e->bkeys_theta, e->bkeys_lik, e->bkeys_prior, e->B, e->M, L);
+  }
   const Key2 carry_lik = key_array_as_carry(e->bkeys_lik, 0), carry_prior = key_array_as_carry(e->bkeys_prior, 0);
-  if (e->hp_tier) batch_edge_scores(e);
-  else launch_edge_scores(e, e->stream, alpha, EdgeFork{}, nullptr);
-  // acyclicity term and kernel matrix on the second stream (both need only this step's z / scores), the likelihood chain on the first
-  const EventFork ef(e);
-  if (ef.fork()) return 1;
-  if (e->hp_tier) batch_acyc(e, ef.s2, carry_prior);
-  else launch_acyc(e, ef.s2, carry_prior, -1, alpha);
-  kmat_batch(e, ef.s2);
-  if (ef.chain_done()) return 1;
-  BgeParams bp = e->bge.params();
-  bp.pM = e->M;
-  {
-    KTimer tm(e, DIBS_K_BGE_NODES);
-    bge_launch_sample_batch(e->stream, e->thr, e->masks, e->node_scores, bp, carry_lik, R, e->d, e->S, e->W, L, e->bq);
-  }
-  {
-    KTimer tm(e, DIBS_K_BGE_BIG);
-    bge_launch_chol_batch(e->stream, e->node_scores, bp, e->bq, e->d, e->S);
-  }
-  if (ef.join()) return 1;
-  const RowTarget rt = packed_rows(e, e->pack);
-  if (e->hp_tier) batch_tail(e, rt);
-  else launch_tail(e, rt, TailOpts{alpha, beta, true, true, e->w_lik, false, nullptr});
-  std::swap(e->baseline, e->baseline2);
-  {
-    // SVGD transform + optimizer step: k_phi_update's BATCH instantiation, grid.y = problem, each problem exactly a standalone launch
-    KTimer tm(e, DIBS_K_PHI_UPDATE);
-    launch_phi_update(e, e->pack, (size_t)e->E, PhiSeg{0, (size_t)e->D, (size_t)e->D, 0, e->z, e->vz, e->phi_z, (float)c.h_latent}, e->M, nullptr, 0);
-  }
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(err));
-  return 0;
-}
-
-// ---- chains engine (n_chains = C > 1, include/dibs_hip.h) ------------------------------------------------------------------------------
-// One step of C chains of one joint model on one data set in the launches of one standalone step: rows [C * M] chain-major.  The data is
-// shared, so every kernel that reads it -- and the edge, acyclicity and tail kernels -- runs unchanged over all rows, with explicit keys
-// (Mg = -1, rng_explicit_row) that k_chain_keys derives from the C device-resident carries.  Chain-aware: the keys, the two block-diagonal
-// kernel matrices [C * M][M] (latent -> kz, theta -> kt and kz + kt -> ksum) and the SVGD transform (k_phi_update's JOINT + BATCH forms,
-// grid.y = chain).  Fork / join of the second stream by events only; every choice a standalone engine makes from its particle count is
-// made from M, one chain's (acyc_cpb, the kernel-matrix algorithm, phi's TA / FULL, JointLaunch::M_choice), never from C * M.
-// With per-chain data (LinearGaussian, dibs_engine_set_data_problem for every chain) the step is the same: the launchers of tu_lin.hip take
-// the per-chain forms of the data-reading kernels (tu_lin_chains.hip) when the workspace holds JointWork::n_chain_data data sets.
-static bool chains_kmat_tiled(const dibs_engine* e) {  // (kmat_tiled_on of a standalone engine of M particles)
-  return e->M >= e->tune.kmat_tiled_min && kmat_tile_addressable((size_t)2 * e->M, e->E > e->Ev ? e->E : e->Ev, 0, 0);
-}
-// Per-chain hyper-parameters (dibs_engine_set_chain_hparams; e->hp_tier of a chains engine: some chain's values differ from the
-// configuration's; LinearGaussian with per-chain data, n_vars, n_dim <= 64): the keys launch also forms every chain's alpha and beta of the
-// step in its row of the table, the edge, acyclicity and tail launches are the table-reading ones of the batched engine with pM = M
-// (batch_edge_scores, batch_acyc; chains_tail below), the kernel matrices take chain p's h / h_theta, phi reads the table as it always did,
-// and the per-chain estimator kernels take alpha and the baseline rate of the block's chain (LinChainData::hp; they always do).  Without
-// differing values the launches below are those of a chains engine on which nothing was set.
-// (the tail of a joint model as launch_tail builds it -- no score-function likelihood, prior terms on, W, U, V in LDS, no riders, no join
-//  flag; alpha, beta, the prior constant, 1 / sigma^2 and the baseline rate: k_particle_grad_batch fills them in from the table)
-static void chains_tail(dibs_engine* e, const RowTarget& rt) {
-  const dibs_config& c = e->cfg;
-  KTimer tm(e, DIBS_K_TAIL);
-  const int ldz = tail_ldz(e->d, e->k, e->S, false, LDS_LIMIT - 2048);
-  const size_t lds = tail_lds_bytes(e->d, ldz, e->S, e->W, false, 0);
-  const TailArgs ta{nullptr, e->masks, e->logprobs_z, e->baseline, e->baseline2, 0.0, nullptr, e->S, e->W, 0, e->probs, e->w_lik,
-                    e->w_acyc, 0.f, 0.f, c.graph_prior, 0.f, e->z, rt.base, rt.stride, rt.copy_vals, 0, e->d, e->k, ldz, 0.f, nullptr, nullptr,
-                    nullptr, 0u, nullptr, e->Mloc,
-                    KmatTile{nullptr, 0, 0, 0, nullptr, 0, 0, 0, 1, 0, 0, 0, 1, 1, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr}};
-  batch_launch_tail(e->stream, ta, e->hp, e->M, e->Mloc, lds);
-}
-int step_chains(dibs_engine* e, int t) {
-  const dibs_config& c = e->cfg;
-  const bool tier = e->hp_tier;
-  const float alpha = (float)(c.alpha_linear * t), beta = (float)(c.beta_linear * t);
-  // (per-chain data: the per-chain estimator kernels read the step's alpha from the table, so the keys launch forms it there also when no
-  //  chain's values differ -- the same launch with two more stores per chain)
-  if (tier || e->jw.n_chain_data) chains_launch_keys_hp(e->stream, e->bcarry, e->bkeys_theta, e->bkeys_lik, e->bkeys_prior, e->B, e->M, c.rng_layout, e->hp, t);
-  else chains_launch_keys(e->stream, e->bcarry, e->bkeys_theta, e->bkeys_lik, e->bkeys_prior, e->B, e->M, c.rng_layout);
-  const Key2 carry_theta = key_array_as_carry(e->bkeys_theta, 0), carry_lik = key_array_as_carry(e->bkeys_lik, 0),
-             carry_prior = key_array_as_carry(e->bkeys_prior, 0);
   if (tier) batch_edge_scores(e);
   else launch_edge_scores(e, e->stream, alpha, EdgeFork{}, nullptr);
-  // acyclicity term and both kernel matrices on the second stream (they need only this step's scores / z / theta), the estimators on the first
+  // acyclicity term and kernel matrices on the second stream (they need only this step's scores / z / theta), the estimators on the first
   const EventFork ef(e);
   if (ef.fork()) return 1;
   if (tier) batch_acyc(e, ef.s2, carry_prior);
   else launch_acyc(e, ef.s2, carry_prior, -1, alpha);
-  {
-    KTimer tm(e, DIBS_K_KMAT, ef.s2);
-    const bool tiled = chains_kmat_tiled(e);
-    if (tier) {
-      chains_launch_kmat_hp(ef.s2, tiled, e->z, (size_t)e->D, e->kz, e->B, e->M, (float)c.scale_latent, e->hp, 0, nullptr, nullptr,
-                            kmat_lds_bytes((size_t)e->D));
-      chains_launch_kmat_hp(ef.s2, tiled, e->theta, (size_t)e->P, e->kt, e->B, e->M, (float)c.scale_theta, e->hp, 1, e->kz, e->ksum,
-                            kmat_lds_bytes((size_t)e->P));
-    } else {
-      chains_launch_kmat(ef.s2, tiled, e->z, (size_t)e->D, e->kz, e->B, e->M, (float)c.scale_latent, (float)c.h_latent, nullptr, nullptr,
-                         kmat_lds_bytes((size_t)e->D));
-      chains_launch_kmat(ef.s2, tiled, e->theta, (size_t)e->P, e->kt, e->B, e->M, (float)c.scale_theta, (float)c.h_theta, e->kz, e->ksum,
-                         kmat_lds_bytes((size_t)e->P));
-    }
-  }
+  if (chains) kmat_chains(e, ef.s2);
+  else kmat_batch(e, ef.s2);
   if (ef.chain_done()) return 1;
   const RowTarget rt = packed_rows(e, e->pack);
-  // (per-chain data: the estimator kernels read alpha and the baseline rate from the table; the two arguments here are not read)
-  if (launch_joint_estimators(e, rt, -1, alpha, carry_theta, carry_lik, e->M, "chains engine (n_chains > 1): ",
-                              ": scratch area: hipMalloc failed, or the partial sums of all chains pass the gradient kernel's addressing limit", true))
-    return 1;
+  if (chains) {
+    // (per-chain data: the estimator kernels read alpha and the baseline rate from the table; the two arguments here are not read)
+    if (launch_joint_estimators(e, rt, -1, alpha, key_array_as_carry(e->bkeys_theta, 0), carry_lik, e->M, "chains engine (n_chains > 1): ",
+                                ": scratch area: hipMalloc failed, or the partial sums of all chains pass the gradient kernel's addressing limit", true))
+      return 1;
+  } else {
+    BgeParams bp = e->bge.params();
+    bp.pM = e->M;
+    {
+      KTimer tm(e, DIBS_K_BGE_NODES);
+      bge_launch_sample_batch(e->stream, e->thr, e->masks, e->node_scores, bp, carry_lik, R, e->d, e->S, e->W, L, e->bq);
+    }
+    KTimer tm(e, DIBS_K_BGE_BIG);
+    bge_launch_chol_batch(e->stream, e->node_scores, bp, e->bq, e->d, e->S);
+  }
   if (ef.join()) return 1;
-  if (tier) chains_tail(e, rt);
-  else launch_tail(e, rt, TailOpts{alpha, beta, false, true, e->w_lik, false, nullptr});
+  const bool score_lik = !chains;
+  if (tier) multi_tail_hp(e, rt, score_lik);
+  else launch_tail(e, rt, TailOpts{alpha, beta, score_lik, true, e->w_lik, false, nullptr});
+  if (score_lik) std::swap(e->baseline, e->baseline2);
   {
+    // SVGD transform + optimizer step: k_phi_update's BATCH instantiations, grid.y = run, each run exactly a standalone launch
     KTimer tm(e, DIBS_K_PHI_UPDATE);
     launch_phi_update(e, e->pack, (size_t)e->E, PhiSeg{0, (size_t)e->D, (size_t)e->D, 0, e->z, e->vz, e->phi_z, (float)c.h_latent}, e->M, nullptr, 0);
-    launch_phi_update(e, e->pack, (size_t)e->E, PhiSeg{(size_t)(2 * e->D), (size_t)(2 * e->D + e->P), (size_t)e->P, 1, e->theta, e->vtheta, e->phi_th,
-                                                       (float)c.h_theta}, e->M, nullptr, 0);
+    if (chains)
+      launch_phi_update(e, e->pack, (size_t)e->E, PhiSeg{(size_t)(2 * e->D), (size_t)(2 * e->D + e->P), (size_t)e->P, 1, e->theta, e->vtheta, e->phi_th,
+                                                         (float)c.h_theta}, e->M, nullptr, 0);
   }
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(err));

@@ -1,8 +1,8 @@
 // How one SVGD step of the float32 engine (step_local / step_update, engine_step.hip) is scheduled, decided ONCE per step and written down
 // as a value: where this step's kernel matrices are computed, how the second stream is forked behind the edge kernel and how it is joined
 // in front of k_particle_grad.  plan_step is a pure function of StepFacts -- plain C++17, nothing of HIP, no allocation, no globals -- so
-// that the whole truth table can be checked on a CPU (tests/tools/step_plan_check.cpp).  step_batch and step_chains keep their own
-// schedule (EventFork, engine_impl.h) and are not planned here.
+// that the whole truth table can be checked on a CPU (tests/tools/step_plan_check.cpp).  step_multi (batched and chains engines) keeps
+// its own schedule (EventFork, engine_impl.h) and is not planned here.
 #pragma once
 #include "../../include/dibs_hip.h"  // DIBS_LIK_*, DIBS_EST_*
 #include "kmat_consts.h"             // KT_T, KMAT_CH, kmat_tile_count, kmat_nchunk

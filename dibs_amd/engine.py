@@ -71,35 +71,37 @@ class Engine:
         mo = None if bge_mean_obs is None else np.ascontiguousarray(bge_mean_obs, np.float32)
         _lib.check(self.lib.dibs_engine_set_data_problem(self._h, int(p), _ptr(x), int(x.shape[0]), _ptr(m), _ptr(mo)))
 
+    def _hparams(self, i, struct, getter, hp=None, setter=None, names=(), what="", kw=None):
+        """What the per-problem and the per-chain accessors share.  Without ``setter``: run i's values (a ``struct``).  With it: set ``hp``
+        -- None: the current values -- with the keywords ``kw`` out of ``names`` on top."""
+        if hp is None:
+            hp = struct()
+            _lib.check(getter(self._h, int(i), C.byref(hp)))
+        if setter is None:
+            return hp
+        for name, v in kw.items():
+            if name not in names:
+                raise TypeError(f"{name} is not a per-{what} setting (one of {', '.join(names)})")
+            setattr(hp, name, float(v))
+        _lib.check(setter(self._h, int(i), C.byref(hp)))
+
     def set_problem_hparams(self, p, hparams=None, **kw):
         """Per-problem hyper-parameters of a batched engine (include/dibs_hip.h, dibs_engine_set_problem_hparams): a ProblemHparams, or
         keywords out of ``_abi.SWEEPABLE`` on top of the problem's current values.  Only before the particles are initialised."""
-        hp = self.get_problem_hparams(p) if hparams is None else hparams
-        for name, v in kw.items():
-            if name not in SWEEPABLE:
-                raise TypeError(f"{name} is not a per-problem setting (one of {', '.join(SWEEPABLE)})")
-            setattr(hp, name, float(v))
-        _lib.check(self.lib.dibs_engine_set_problem_hparams(self._h, int(p), C.byref(hp)))
+        self._hparams(p, ProblemHparams, self.lib.dibs_engine_get_problem_hparams, hparams, self.lib.dibs_engine_set_problem_hparams,
+                      SWEEPABLE, "problem", kw)
 
     def get_problem_hparams(self, p):
-        hp = ProblemHparams()
-        _lib.check(self.lib.dibs_engine_get_problem_hparams(self._h, int(p), C.byref(hp)))
-        return hp
+        return self._hparams(p, ProblemHparams, self.lib.dibs_engine_get_problem_hparams)
 
     def set_chain_hparams(self, c, hparams=None, **kw):
         """Per-chain hyper-parameters of a chains engine (include/dibs_hip.h, dibs_engine_set_chain_hparams): a ChainHparams, or keywords
         out of ``_abi.JOINT_SWEEPABLE`` on top of the chain's current values.  Only before the particles are initialised."""
-        hp = self.get_chain_hparams(c) if hparams is None else hparams
-        for name, v in kw.items():
-            if name not in JOINT_SWEEPABLE:
-                raise TypeError(f"{name} is not a per-chain setting (one of {', '.join(JOINT_SWEEPABLE)})")
-            setattr(hp, name, float(v))
-        _lib.check(self.lib.dibs_engine_set_chain_hparams(self._h, int(c), C.byref(hp)))
+        self._hparams(c, ChainHparams, self.lib.dibs_engine_get_chain_hparams, hparams, self.lib.dibs_engine_set_chain_hparams,
+                      JOINT_SWEEPABLE, "chain", kw)
 
     def get_chain_hparams(self, c):
-        hp = ChainHparams()
-        _lib.check(self.lib.dibs_engine_get_chain_hparams(self._h, int(c), C.byref(hp)))
-        return hp
+        return self._hparams(c, ChainHparams, self.lib.dibs_engine_get_chain_hparams)
 
     def init_particles_batch(self, keys):
         keys = np.ascontiguousarray(np.asarray(keys, np.uint32).reshape(self.B, 2))

@@ -5,6 +5,7 @@ For a ``JointDiBS`` model this is the chains engine (include/dibs_hip.h, n_chain
 are shared, only the keys differ.  A ``MarginalDiBS`` model goes to ``sample_batch([model] * C, keys=...)``, the batched engine."""
 import numpy as np
 
+from . import _multirun
 from .. import random
 from ..engine import Engine
 from .svgd import JointDiBS, MarginalDiBS
@@ -42,13 +43,14 @@ def sample_chains(model, *, keys, n_particles, steps, n_dim_particles=None, call
         raise ValueError("sample_chains: float64 models are not supported (the float64 engine runs one chain; use sample())")
     keys = _chain_keys(keys)
     kw = dict(n_particles=n_particles, steps=steps, n_dim_particles=n_dim_particles, callback=callback, callback_every=callback_every)
-    if len(keys) == 1:  # (one chain is the standalone engine)
-        out = [model.sample(key=keys[0], **kw)]
-        model.last_chain_states = [model.last_state]
-        return out
-    if isinstance(model, MarginalDiBS):
+    if isinstance(model, MarginalDiBS) and len(keys) > 1:
         return _marginal_chains(model, keys, kw)
-    return _run_chains(model, keys, n_particles, n_dim_particles or model.n_vars, steps, callback, callback_every)
+    cfg = model._make_config(n_particles, n_dim_particles or model.n_vars)
+    # (one table of an edge-wise graph prior: the chains share it, as they share the data)
+    edge_probs = model.graph_model.edge_probs if _multirun._edgewise(model) else None
+    out, states = _multirun.sample_runs(Engine, cfg, "chains", [model] * len(keys), keys, data="shared", edge_probs=edge_probs, **kw)
+    model.last_chain_states = states or [model.last_state]   # (one chain: sample() has left its state there)
+    return out
 
 
 def _marginal_chains(model, keys, kw):
@@ -65,40 +67,4 @@ def _marginal_chains(model, keys, kw):
     model.last_chain_states = [c.last_state for c in clones]
     if model.latent_prior_std is None:
         model.latent_prior_std = clones[0].latent_prior_std
-    return out
-
-
-def _run_chains(model, keys, n_particles, n_dim, steps, callback, callback_every):
-    C, d = len(keys), model.n_vars
-    cfg = model._make_config(n_particles, n_dim)
-    cfg.reserved_i[2] = C
-    eng = Engine(cfg)
-    try:
-        eng.set_data(model.x, model.interv_mask if model.interv_mask.any() else None, None)
-        if model.graph_model._dibs_prior == "edgewise":   # (one table: the chains share it)
-            eng.set_edge_prior(model.graph_model.edge_probs)
-        eng.init_particles_batch(np.stack([np.asarray(k, np.uint32).reshape(2) for k in keys]))
-        if model.latent_prior_std is None:
-            model.latent_prior_std = float(np.float32(1.0) / np.sqrt(np.float32(n_dim)))
-        callback_every = callback_every or steps
-        for t in (range(0, steps, callback_every) if steps else range(0)):
-            eng.run(t, callback_every)
-            if callback:
-                st = eng.get_state()
-                z, th = st["z"].reshape(C, n_particles, d, n_dim, 2), st["theta"].reshape(C, n_particles, -1)
-                for c in range(C):
-                    callback(dibs=model, t=t + callback_every, zs=z[c], thetas=model._theta_out(th[c]))
-        st = eng.get_state()
-    finally:
-        eng.close()
-    zshape = (C, n_particles, d, n_dim, 2)
-    z, v_z = st["z"].reshape(zshape), st["v_z"].reshape(zshape)
-    th, v_th = st["theta"].reshape(C, n_particles, -1), st["v_theta"].reshape(C, n_particles, -1)
-    base = st["baseline"].reshape(C, n_particles)
-    states, out = [], []
-    for c in range(C):
-        s = dict(z=z[c].copy(), v_z=v_z[c].copy(), theta=th[c].copy(), v_theta=v_th[c].copy(), key=st["key"][c].copy(), baseline=base[c].copy())
-        states.append(s)
-        out.append((model.particle_to_g_lim(s["z"]), model._theta_out(s["theta"])))
-    model.last_chain_states = states
     return out

@@ -10,6 +10,7 @@ from .._abi import make_config
 from ..engine import Engine
 from ..kernel import AdditiveFrobeniusSEKernel, JointAdditiveFrobeniusSEKernel
 from ..metrics import ParticleDistribution
+from ._multirun import chunks, default_latent_prior_std
 from .dibs import DiBS
 
 
@@ -182,13 +183,12 @@ class _SVGDBase(DiBS):
         try:
             eng.init_particles(key)
             if self.latent_prior_std is None:
-                self.latent_prior_std = float(np.float32(1.0) / np.sqrt(np.float32(n_dim)))
-            callback_every = callback_every or steps
-            for t in (range(0, steps, callback_every) if steps else range(0)):
-                eng.run(t, callback_every)
+                self.latent_prior_std = default_latent_prior_std(n_dim)
+            for t, n in chunks(steps, callback_every):
+                eng.run(t, n)
                 if callback:
                     st = eng.get_state()
-                    kw = dict(dibs=self, t=t + callback_every, zs=st["z"])
+                    kw = dict(dibs=self, t=t + n, zs=st["z"])
                     if self._joint:
                         kw["thetas"] = self._theta_out(st["theta"])
                     callback(**kw)

@@ -5,11 +5,9 @@ dibs_engine_set_problem_hparams).
 kernel bandwidth ``h``, optimizer step size, ``score_function_baseline``, ``latent_prior_std`` and ``n_edges_per_node`` of the graph
 prior -- the scalars a kernel takes as a launch argument, which select no size, code path or buffer.  Everything else is shared as in
 ``sample_batch``.  Entry i of the result equals ``models[i].sample(key=keys[i], ...)`` bit for bit."""
+from . import _multirun
 from .._abi import SWEEPABLE, problem_hparams
-from .batch import _batchable, _run_batched, _shared_fields
-
-# beyond these sizes the engine's kernels take the per-problem values as launch arguments of the whole batch (include/dibs_hip.h)
-_MAX_VARS = 64
+from .batch import _batchable, _sample
 
 
 def _plan(models, keys, n_particles, n_dim_particles):
@@ -19,16 +17,8 @@ def _plan(models, keys, n_particles, n_dim_particles):
         return keys, None, None, []
     n_dim = n_dim_particles or models[0].n_vars
     cfgs = [m._make_config(n_particles, n_dim) for m in models]
-    fields = [_shared_fields(c) for c in cfgs]   # (latent_prior_std: the default filled in)
-    for i, got in enumerate(fields[1:], 1):
-        diff = [k for k in fields[0] if k not in SWEEPABLE and fields[0][k] != got[k]]
-        if diff:
-            raise ValueError(f"sample_sweep: model {i} differs from model 0 in {', '.join(diff)} (a sweep shares every size, the prior "
-                             f"and optimizer kind, tau and the BGe parameters; per problem: {', '.join(SWEEPABLE)})")
-    swept = [k for k in SWEEPABLE if any(f[k] != fields[0][k] for f in fields[1:])]
-    if swept and (cfgs[0].n_vars > _MAX_VARS or cfgs[0].n_dim > _MAX_VARS):
-        raise ValueError(f"sample_sweep: models differ in {', '.join(swept)}, which needs n_vars <= {_MAX_VARS} and "
-                         f"n_dim_particles <= {_MAX_VARS} (got {cfgs[0].n_vars}, {cfgs[0].n_dim})")
+    _multirun.check_shared(cfgs, SWEEPABLE, "sample_sweep", "a sweep shares every size, the prior and optimizer kind, tau and the BGe "
+                           f"parameters; per problem: {', '.join(SWEEPABLE)}")
     return keys, n_dim, cfgs[0], [problem_hparams(c) for c in cfgs]
 
 
@@ -39,10 +29,8 @@ def sample_sweep(models, *, keys, n_particles, steps, n_dim_particles=None, call
     ``last_state`` are those of ``sample_batch``.  The usual call is a grid: one model object per grid point on the same data, times a
     few keys."""
     models = list(models)
-    keys, n_dim, cfg, hparams = _plan(models, keys, n_particles, n_dim_particles)
+    keys, _, cfg, hparams = _plan(models, keys, n_particles, n_dim_particles)
     if not models:
         return []
-    if len(models) == 1:  # (a sweep of one is the standalone engine)
-        return [models[0].sample(key=keys[0], n_particles=n_particles, steps=steps, n_dim_particles=n_dim_particles,
-                                 callback=callback, callback_every=callback_every)]
-    return _run_batched(models, keys, cfg, n_particles, n_dim, steps, callback, callback_every, hparams=hparams)
+    return _sample(models, keys, cfg, hparams=hparams, n_particles=n_particles, steps=steps, n_dim_particles=n_dim_particles,
+                   callback=callback, callback_every=callback_every)
