@@ -14,10 +14,27 @@ ACT = {"relu": 0, "tanh": 1, "sigmoid": 2, "leakyrelu": 3}
 
 BUF = dict(Z=0, V_Z=1, THETA=2, V_THETA=3, SCORES=4, LOGPROBS_Z=5, W_LIK=6, W_ACYC=7, GRAD_Z=8,
            GRAD_THETA=9, KXX=10, PHI_Z=11, BASELINE=12, NODE_SCORES=13, PARENT_MASKS=14,
-           LOGPROBS_THETA=15, PHI_THETA=16, GATHER=17, PROBLEM_STEP=18)
+           LOGPROBS_THETA=15, PHI_THETA=16, GATHER=17, PROBLEM_STEP=18, BANDWIDTH=19, SQDIST_Z=20, SQDIST_THETA=21)
 KERNELS = ["edge", "bge_nodes", "lik_weights", "acyc", "zgrad", "kmat", "phi_update", "lin_logprobs",
-           "lin_grad", "nn_theta", "nn_z", "pack", "bge_big", "acyc_reduce", "particle_grad", "k15"]
+           "lin_grad", "nn_theta", "nn_z", "pack", "bge_big", "acyc_reduce", "particle_grad", "bandwidth"]
 K_COUNT = 16
+# dibs_config.reserved_i[3], the kernel bandwidth rule: which kernels take h = median ||x_a - x_b||^2 / log(M + 1) (include/dibs_hip.h)
+MEDIAN = "median"
+BW_MEDIAN_LATENT, BW_MEDIAN_THETA = 1, 2
+
+
+def bandwidth_rule(h_latent, h_theta):
+    """(reserved_i[3], h_latent, h_theta as floats) of a pair of bandwidth settings, each a number or the string "median"; a segment on the
+    median rule carries the reference's default in its float field, which the engine does not read."""
+    rule, out = 0, []
+    for h, bit, default in ((h_latent, BW_MEDIAN_LATENT, 5.0), (h_theta, BW_MEDIAN_THETA, 500.0)):
+        if isinstance(h, str):
+            if h != MEDIAN:
+                raise ValueError(f"kernel bandwidth must be a number or {MEDIAN!r}, got {h!r}")
+            rule |= bit
+            h = default
+        out.append(float(h))
+    return rule, out[0], out[1]
 
 
 class DibsConfig(C.Structure):
@@ -110,7 +127,8 @@ def make_config(*, n_vars, n_particles, n_observations, n_dim=None, joint=False,
     """Build a dibs_config with the reference's defaults (svgd.py:60-83 marginal, :425-448 joint).  ``n_problems`` > 1: a batched
     engine of that many independent problems of ``n_particles`` particles each (include/dibs_hip.h, reserved_i[0]).  ``precision``
     64: the float64 engine (reserved_i[1]; 32 = float32, the default).  ``n_chains`` > 1: a chains engine of that many chains of one
-    joint model on one data set, ``n_particles`` particles each (reserved_i[2]; 0 or 1: the standalone engine)."""
+    joint model on one data set, ``n_particles`` particles each (reserved_i[2]; 0 or 1: the standalone engine).  ``h_latent`` / ``h_theta``
+    ``"median"``: that kernel's bandwidth by the median heuristic, selected on the device every step (reserved_i[3])."""
     c = DibsConfig()
     c.abi_version = ABI_VERSION
     c.n_vars = int(n_vars)
@@ -144,7 +162,8 @@ def make_config(*, n_vars, n_particles, n_observations, n_dim=None, joint=False,
     c.alpha_linear = float((0.05 if joint else 1.0) if alpha_linear is None else alpha_linear)
     c.beta_linear = float(beta_linear)
     c.tau = float(tau)
-    c.h_latent, c.h_theta = float(h_latent), float(h_theta)
+    # (either bandwidth may be "median": the rule bits; a marginal model has no parameter kernel -- the engine refuses the bit there)
+    c.reserved_i[3], c.h_latent, c.h_theta = bandwidth_rule(h_latent, h_theta)
     c.scale_latent, c.scale_theta = float(scale_latent), float(scale_theta)
     c.stepsize = float(stepsize)
     c.score_function_baseline = float(score_function_baseline)

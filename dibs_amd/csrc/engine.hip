@@ -51,6 +51,7 @@ static dibs_chain_hparams config_hparams(const dibs_config& c) {
 // queue holds up the kernels behind it, possibly the one it waits for, until its bound: those engines use events.  DIBS_FLAGS_MULTI=1 lifts
 // the rule (scripts/gpu_shard_scaling.py: what a rank of a real run would do).
 static std::atomic<int> g_live_engines{0};
+static ProblemHP derive_problem_hp(const dibs_engine* e, const dibs_chain_hparams& h);  // (below, with the per-problem accessors)
 // sizes, stream, events and every device buffer of a new engine; on failure the caller destroys the half-built engine
 static int engine_alloc(dibs_engine* e, const dibs_config& c, void* stream) {
   e->cfg = c;
@@ -210,6 +211,19 @@ static int engine_alloc(dibs_engine* e, const dibs_config& c, void* stream) {
     HIP_OK(dalloc(&e->hp, (size_t)e->B));
     e->hp_host.assign((size_t)e->B, config_hparams(c));
   }
+  e->median_rule = c.reserved_i[3];
+  if (e->median_rule) {
+    if (e->B == 1) {  // a standalone engine on the rule: a one-row table of the configuration's values, final from the start
+      HIP_OK(dalloc(&e->hp, (size_t)1));
+      e->hp_host.assign((size_t)1, config_hparams(c));
+      const ProblemHP row = derive_problem_hp(e, e->hp_host[0]);
+      HIP_OK(hipMemcpy(e->hp, &row, sizeof row, hipMemcpyHostToDevice));
+      e->hp_final = true;
+    }
+    if (e->median_rule & 1) HIP_OK(dalloc(&e->sqd_z, Ml * e->M));
+    if (e->median_rule & 2) HIP_OK(dalloc(&e->sqd_t, Ml * e->M));
+    HIP_OK(dalloc(&e->bw, (size_t)2 * e->B));
+  }
   // (k_phi_gemm reads whole 128-row x 32-column tiles without bounds checks: rows padded to a multiple of 128, one more tile row of slack)
   const size_t kpad = (((Ml + 127) / 128) * 128 - Ml) * e->M + 64;
   HIP_OK(dalloc(&e->kz, Ml * e->M + kpad));
@@ -263,6 +277,19 @@ extern "C" int dibs_engine_create(const dibs_config* cfg, void* stream, dibs_eng
   *out = nullptr;
   const dibs_config& c = *cfg;
   if (c.abi_version != DIBS_ABI_VERSION) return fail("dibs_config.abi_version mismatch");
+  if (c.reserved_i[3] != 0) {
+    // median-heuristic kernel bandwidth (reserved_i[3]: bit 0 the latent kernel, bit 1 the parameter kernel; include/dibs_hip.h)
+    const std::string pre = "median bandwidth: ";
+    const int rule = c.reserved_i[3];
+    if (rule < 0 || rule > 3) return fail(pre + "dibs_config.reserved_i[3] (bandwidth rule) must be 0 .. 3 (bit 0: latent kernel, bit 1: parameter kernel), got " + std::to_string(rule));
+    if ((rule & 2) && !c.joint) return fail(pre + "bit 1 (the parameter kernel) needs a joint model; a marginal model has no parameter kernel");
+    if (c.reserved_i[1] == 64) return fail(pre + "the float64 engine is not supported (float32 only)");
+    if (c.n_ranks > 1) return fail(pre + "n_ranks must be 1 (the selection needs the distances of all particles; a sharded run holds a slab)");
+    if (c.n_particles >= 256)
+      return fail(pre + "n_particles (per run) must be < 256: the GEMM form of the SVGD transform (k_phi_gemm) has no table-reading form and the "
+                        "selection is one block per run -- both are the follow-up");
+    if (c.n_particles < 2) return fail(pre + "n_particles must be >= 2 (one particle has no pair to take a median of)");
+  }
   {
     // chains engine (reserved_i[2] = n_chains = C > 1, include/dibs_hip.h): C chains of one joint model on one data set, one rank, float32
     const int64_t C = c.reserved_i[2];
@@ -409,7 +436,7 @@ extern "C" int dibs_engine_destroy(dibs_engine* e) {
   if (e->stream2) hipStreamSynchronize(e->stream2);
   void* ptrs[] = {e->z, e->vz, e->theta, e->vtheta, e->baseline, e->baseline2, e->scores, e->probs, e->eas, e->thr, e->w_lik, e->acyc_part, e->w_acyc,
                   e->logprobs_z, e->logprobs_th, e->pack, e->kz, e->kt, e->phi_z, e->phi_th, e->counters, e->masks,
-                  e->node_scores, e->x, e->mask, e->bq.list, e->bq.counts, e->soft_ds, e->acyc_big, e->w_tot, e->join_flag, e->fork_flag, e->carry_bak, e->soft_tri, e->ksum, e->kpart, e->kmat_ctr, e->bcarry, e->bkeys_lik, e->bkeys_prior, e->bkeys_theta, e->hp, e->edge_tab, e->edge_tab64};
+                  e->node_scores, e->x, e->mask, e->bq.list, e->bq.counts, e->soft_ds, e->acyc_big, e->w_tot, e->join_flag, e->fork_flag, e->carry_bak, e->soft_tri, e->ksum, e->kpart, e->kmat_ctr, e->bcarry, e->bkeys_lik, e->bkeys_prior, e->bkeys_theta, e->hp, e->edge_tab, e->edge_tab64, e->sqd_z, e->sqd_t, e->bw};
   for (void* p : ptrs)
     if (p) hipFree(p);
   joint_free(&e->jw);
@@ -889,6 +916,9 @@ static BufInfo buf_info(const dibs_engine* e, int which) {
     case DIBS_BUF_GRAD_Z: return {nullptr, Ml * e->D * 4};
     case DIBS_BUF_GRAD_THETA: return {nullptr, Ml * e->P * 4};
     case DIBS_BUF_PROBLEM_STEP: return {nullptr, e->B > 1 ? (int64_t)e->B * 8 : -1};  // (alpha, beta) out of the table's rows
+    case DIBS_BUF_BANDWIDTH: return {nullptr, (int64_t)e->B * 8};  // (h_latent, h_theta) per run: configuration / table values, median segments from e->bw
+    case DIBS_BUF_SQDIST_Z: return {e->sqd_z, e->sqd_z ? Ml * e->M * 4 : -2};  // (-2: the segment is not on the median rule)
+    case DIBS_BUF_SQDIST_THETA: return {e->sqd_t, e->sqd_t ? Ml * e->M * 4 : -2};
     default: return {nullptr, -1};
   }
 }
@@ -900,6 +930,7 @@ extern "C" int dibs_engine_read_buffer(dibs_engine* e, int32_t which, void* host
   HIP_OK(hipSetDevice(e->cfg.device_id));
   HIP_OK(hipStreamSynchronize(e->stream));
   const BufInfo bi = buf_info(e, which);
+  if (bi.bytes == -2) return fail("no such buffer (the squared distances exist only for a segment on the median bandwidth rule, dibs_config.reserved_i[3])");
   if (bi.bytes < 0) return fail(e->f64 ? "float64 engine: no such buffer (theta / packed / gathered rows belong to the float32 engine)" : "unknown buffer id");
   if (bi.bytes != nbytes) return fail("buffer size mismatch: expected " + std::to_string(bi.bytes) + " bytes");
   if (nbytes == 0) return 0;
@@ -911,6 +942,24 @@ extern "C" int dibs_engine_read_buffer(dibs_engine* e, int32_t which, void* host
   }
   if (which == DIBS_BUF_PROBLEM_STEP) {
     HIP_OK(hipMemcpy2D(host, 8, (const char*)e->hp + offsetof(ProblemHP, alpha), sizeof(ProblemHP), 8, (size_t)e->B, hipMemcpyDeviceToHost));
+    return 0;
+  }
+  if (which == DIBS_BUF_BANDWIDTH) {
+    // fixed rule: the values the launches take (the configuration's, or a run's own: per-problem / per-chain hyper-parameters); a segment
+    // on the median rule: what the selection of the last step wrote (zeros before the first step)
+    float* out = (float*)host;
+    for (int p = 0; p < e->B; ++p) {
+      const bool own = !e->hp_host.empty();
+      out[2 * p] = (float)(own ? e->hp_host[(size_t)p].h_latent : e->cfg.h_latent);
+      out[2 * p + 1] = (float)(own ? e->hp_host[(size_t)p].h_theta : e->cfg.h_theta);
+    }
+    if (e->median_rule) {
+      std::vector<float> dev((size_t)2 * e->B);
+      HIP_OK(hipMemcpy(dev.data(), e->bw, dev.size() * 4, hipMemcpyDeviceToHost));
+      for (int p = 0; p < e->B; ++p)
+        for (int s = 0; s < 2; ++s)
+          if (e->median_rule >> s & 1) out[2 * p + s] = dev[(size_t)2 * p + s];
+    }
     return 0;
   }
   if (which == DIBS_BUF_KXX && e->kt) {  // kxx = k_z + k_theta

@@ -106,6 +106,12 @@ struct dibs_engine {
   std::vector<dibs_chain_hparams> hp_host;
   ProblemHP* hp = nullptr;  // [B]
   bool hp_final = false, hp_tier = false, chain_hp_ok = false;
+  // median-heuristic kernel bandwidth (cfg.reserved_i[3]: bit 0 latent, bit 1 theta).  The kernel matrices and phi
+  // read h / h_theta from the table: a standalone engine on the rule owns a one-row table (B = 1) and launches the table-reading forms
+  // with one run.  Every step: distance pass -> sqd_z / sqd_t, selection -> the rows of hp and bw, kernel matrices (launch_bandwidth)
+  int median_rule = 0;
+  float *sqd_z = nullptr, *sqd_t = nullptr;  // [Mloc][M] squared distances (float)tot of the last step, block-diagonal per run
+  float* bw = nullptr;                       // [B][2] (h_latent, h_theta) the last step's kernel matrices used
   struct BatchStats {                                 // host copies of the stacked BGe statistics (padded to d matrices per problem)
     std::vector<float> Rp, Qp;
     std::vector<double> gam, Nj, ldR;
@@ -381,6 +387,10 @@ void chains_launch_keys_hp(hipStream_t st, Key2* carry, Key2* keys_theta, Key2* 
 void chains_launch_kmat_hp(hipStream_t st, bool tiled, const float* x, size_t len, float* kout, int C, int M, float scale, const ProblemHP* hp,
                            int theta_seg, const float* kadd, float* ksum, size_t lds_direct);
 bool chains_hp_differ(const dibs_engine* e);  // (engine.hip: some chain's host values derive to other scalars than the configuration's)
+// ---- tu_batch.hip: median-heuristic bandwidth -- squared distances of one segment of every run (grids of chains_launch_kmat), and the
+// selection that writes h / h_theta of every run's table row and bw [C][2] (rule: dibs_config.reserved_i[3]) ----
+void bandwidth_launch_sqdist(hipStream_t st, bool tiled, const float* x, size_t len, float* out, int C, int M, size_t lds_direct);
+void bandwidth_launch_select(hipStream_t st, const float* sqd_z, const float* sqd_t, int rule, int C, int M, ProblemHP* hp, float* bw);
 // ---- engine_f64.hip ----
 int f64_alloc(dibs_engine* e);
 int f64_init_particles(dibs_engine* e, Key2 isub);

@@ -191,11 +191,33 @@ struct KmatRows {
   size_t stride, off;
 };
 static size_t kmat_lds_bytes(size_t len) { return (size_t)(((len < KMAT_CH ? len : (size_t)KMAT_CH) + 3) & ~(size_t)3) * 4; }
+static bool multi_kmat_tiled(const dibs_engine* e);  // (below, with the multi-run steps)
+// Median-rule bandwidth (dibs_config.reserved_i[3]; kernels and launchers in tu_batch.hip): on `st`, in front of the kernel matrices, the
+// squared distances of every segment on the rule and the selection that writes h / h_theta of every run's table row and e->bw.  Reads
+// e->z / e->theta, which are final when a step starts and are what the packed rows of phase B hold (one rank).  e->B runs: 1 = a
+// standalone engine with its one-row table
+static void launch_bandwidth(dibs_engine* e, hipStream_t st) {
+  KTimer tm(e, DIBS_K_BANDWIDTH, st);
+  const bool tiled = multi_kmat_tiled(e);
+  if (e->median_rule & 1) bandwidth_launch_sqdist(st, tiled, e->z, (size_t)e->D, e->sqd_z, e->B, e->M, kmat_lds_bytes((size_t)e->D));
+  if (e->median_rule & 2) bandwidth_launch_sqdist(st, tiled, e->theta, (size_t)e->P, e->sqd_t, e->B, e->M, kmat_lds_bytes((size_t)e->P));
+  bandwidth_launch_select(st, e->sqd_z, e->sqd_t, e->median_rule, e->B, e->M, e->hp, e->bw);
+}
 // This engine's kernel-matrix slab(s) on `st`: the latent one, then for the joint models theta's with kz / ksum.
 // tiled (kernels_kmat.h: partial sums per 32 x 32 tile and chunk, then one finishing block per row) from 128 particles: config 4 597 ->
 // 645 steps/s, config 5 108.5 -> 115, config 3 2290 -> 2328 on the same box (each row is read once per tile instead of once per pair)
 static void launch_kmat(dibs_engine* e, hipStream_t st, const KmatRows& z, const KmatRows& th) {
   const dibs_config& c = e->cfg;
+  if (e->median_rule) {
+    // median rule (launch_bandwidth has run on `st`): the table-reading forms of the chains engine with ONE run -- the same block
+    // functions, the bandwidth from the engine's one-row table; rows from e->z / e->theta (see launch_bandwidth)
+    const bool tiled = multi_kmat_tiled(e);
+    chains_launch_kmat_hp(st, tiled, e->z, (size_t)e->D, e->kz, 1, e->M, (float)c.scale_latent, e->hp, 0, nullptr, nullptr, kmat_lds_bytes((size_t)e->D));
+    if (c.joint)
+      chains_launch_kmat_hp(st, tiled, e->theta, (size_t)e->P, e->kt, 1, e->M, (float)c.scale_theta, e->hp, 1, e->kz, e->ksum,
+                            kmat_lds_bytes((size_t)e->P));
+    return;
+  }
   if (kmat_tiled_on(e)) {
     kmat_launch_tiled(e, st, z.base, z.stride, z.off, (size_t)e->D, e->kz, (float)c.scale_latent, (float)c.h_latent, nullptr, nullptr);
     if (c.joint) kmat_launch_tiled(e, st, th.base, th.stride, th.off, (size_t)e->P, e->kt, (float)c.scale_theta, (float)c.h_theta, e->kz, e->ksum);
@@ -340,6 +362,8 @@ static void launch_phi_update(dibs_engine* e, const float* pack, size_t stride, 
   const float* const kw = e->kt ? e->ksum : e->kz;
   const float* const kseg = e->kt ? (s.is_theta ? e->kt : e->kz) : nullptr;
   // FULL: whole 8-pair batches per wave and whole particle groups (no clamps inside the kernel)
+  // (the table forms: multi-run engines, and a standalone engine whose bandwidth the median rule writes into its one-row table -- grid.y = 1)
+  const bool table = e->B > 1 || e->median_rule != 0;
   const bool full = e->M % 64 == 0 && rows % ta == 0 && (size_t)e->M * stride * 4 < ((size_t)1 << 32);  // (32-bit buffer offsets)
 #define PHI_LAUNCH(TA_, F_, J_, B_)                                                                                                        \
   {                                                                                                                                        \
@@ -350,8 +374,8 @@ static void launch_phi_update(dibs_engine* e, const float* pack, size_t stride, 
                        (int)cols, ngroups, vals_send, vals_stride, s.is_theta ? (size_t)e->D : (size_t)0);                                 \
   }
 #define PHI_PICK(TA_)                                                                                                                      \
-  if (e->B > 1 && e->kt) { if (full) PHI_LAUNCH(TA_, true, true, true) else PHI_LAUNCH(TA_, false, true, true) }                           \
-  else if (e->B > 1) { if (full) PHI_LAUNCH(TA_, true, false, true) else PHI_LAUNCH(TA_, false, false, true) }                             \
+  if (table && e->kt) { if (full) PHI_LAUNCH(TA_, true, true, true) else PHI_LAUNCH(TA_, false, true, true) }                              \
+  else if (table) { if (full) PHI_LAUNCH(TA_, true, false, true) else PHI_LAUNCH(TA_, false, false, true) }                                \
   else if (e->kt) { if (full) PHI_LAUNCH(TA_, true, true, false) else PHI_LAUNCH(TA_, false, true, false) }                                \
   else { if (full) PHI_LAUNCH(TA_, true, false, false) else PHI_LAUNCH(TA_, false, false, false) }
   if (ta == 16) { PHI_PICK(16) } else if (ta == 8) { PHI_PICK(8) } else { PHI_PICK(4) }
@@ -394,6 +418,7 @@ static StepFacts step_facts(const dibs_engine* e, bool xk, int terms) {
   f.kmat_tiled_min = e->tune.kmat_tiled_min;
   f.no_kmat_fuse = e->tune.no_kmat_fuse;
   f.no_kmat_grad = e->tune.no_kmat_grad;
+  f.median_h = e->median_rule != 0;
   return f;
 }
 
@@ -450,6 +475,7 @@ int step_local(dibs_engine* e, int t, const RowTarget& rt, const StepKeys* xk, i
       hipEventRecord(e->ev_k0, e->stream);
       hipStreamWaitEvent(e->stream2, e->ev_k0, 0);
     }
+    if (e->median_rule) launch_bandwidth(e, e->stream2);  // (distance pass -> selection -> kernel matrices, one stream)
     KTimer tm(e, DIBS_K_KMAT, e->stream2);
     // (Mloc == M here, so m0 == 0 and the slab is the whole symmetric matrix: the arguments launch_kmat derives are the literal 0 and 1)
     launch_kmat(e, e->stream2, KmatRows{e->z, (size_t)e->D, 0}, KmatRows{e->theta, (size_t)e->P, 0});
@@ -528,6 +554,7 @@ int step_update(dibs_engine* e, int t, const RowSource& rs, float* vals_send) {
   KmatPlace place = e->kmat_place;
   if (place == KmatPlace::External || place == KmatPlace::PhaseB) place = kmat_ext ? KmatPlace::External : KmatPlace::PhaseB;
   if (place == KmatPlace::PhaseB) {
+    if (e->median_rule) launch_bandwidth(e, e->stream);
     KTimer tm(e, DIBS_K_KMAT);
     launch_kmat(e, e->stream, KmatRows{pack, rs.stride, rs.z_off}, KmatRows{pack, rs.stride, rs.th_off});
   }
@@ -668,7 +695,7 @@ static void kmat_chains(dibs_engine* e, hipStream_t st) {
   const dibs_config& c = e->cfg;
   KTimer tm(e, DIBS_K_KMAT, st);
   const bool tiled = multi_kmat_tiled(e);
-  if (e->hp_tier) {
+  if (e->hp_tier || e->median_rule) {  // (median rule: the selection has written every chain's h / h_theta of this step)
     chains_launch_kmat_hp(st, tiled, e->z, (size_t)e->D, e->kz, e->B, e->M, (float)c.scale_latent, e->hp, 0, nullptr, nullptr,
                           kmat_lds_bytes((size_t)e->D));
     chains_launch_kmat_hp(st, tiled, e->theta, (size_t)e->P, e->kt, e->B, e->M, (float)c.scale_theta, e->hp, 1, e->kz, e->ksum,
@@ -703,6 +730,7 @@ int step_multi(dibs_engine* e, int t) {
   if (ef.fork()) return 1;
   if (tier) batch_acyc(e, ef.s2, carry_prior);
   else launch_acyc(e, ef.s2, carry_prior, -1, alpha);
+  if (e->median_rule) launch_bandwidth(e, ef.s2);
   if (chains) kmat_chains(e, ef.s2);
   else kmat_batch(e, ef.s2);
   if (ef.chain_done()) return 1;
@@ -793,6 +821,9 @@ extern "C" int dibs_engine_kmat_values(dibs_engine* e, const void* vals_all_dev,
   if (e->f64) return fail("float64 engine: dibs_engine_kmat_values is not supported (dibs_engine_run only)");
   if (refuse_chains(e, "dibs_engine_kmat_values (only dibs_engine_run steps it)")) return 1;
   if (e->B > 1) return fail("batched engine: only dibs_engine_run steps it");
+  if (e->median_rule)
+    return fail("median bandwidth: dibs_engine_kmat_values is not supported (a slab computed beside phase A has no selected bandwidth; the "
+                "rule runs on one rank, where dibs_engine_run / step_local + step_update compute the matrices themselves)");
   HIP_OK(hipSetDevice(e->cfg.device_id));
   const float* vals = (const float*)vals_all_dev;
   launch_kmat(e, (hipStream_t)stream, KmatRows{vals, (size_t)e->Ev, 0}, KmatRows{vals, (size_t)e->Ev, (size_t)e->D});

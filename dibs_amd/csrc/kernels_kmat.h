@@ -146,7 +146,7 @@ __device__ __forceinline__ void kt_stage(float* __restrict__ smem, int clen, int
 }
 // units first, first + step, ... of nta (x ntb) tiles x nsplit pieces; one flat sequence of (unit, chunk) steps with the next step's rows
 // in flight
-template <bool VEC>
+template <bool VEC, bool DIST = false>
 __device__ __forceinline__ void kmat_tile_loop(float* __restrict__ smem, const KmatTile& K, int first, int step, int units, int tid) {
   typedef float f32x2 __attribute__((ext_vector_type(2)));
   const int lane = tid & 63, wave = tid >> 6, ag = lane >> 3, bg = lane & 7;
@@ -209,7 +209,9 @@ __device__ __forceinline__ void kmat_tile_loop(float* __restrict__ smem, const K
           else
             K.part[((size_t)sp * K.Mloc + a) * K.M + b] = tot;
         } else {
-          const float kv = (float)((double)K.scale * exp(-tot / (double)K.h));
+          float kv;
+          if constexpr (DIST) kv = (float)tot;  // (the distance pass: see kmat_block)
+          else kv = (float)((double)K.scale * exp(-tot / (double)K.h));
           const bool mirror = K.symmetric && Ucur.b0 > Ucur.a0;  // (diagonal tiles hold both orders of their pairs: the same sums)
           K.kout[(size_t)a * K.M + b] = kv;
           if (mirror) K.kout[(size_t)b * K.M + a] = kv;
@@ -250,7 +252,9 @@ __device__ __forceinline__ void kmat_tile_loop(float* __restrict__ smem, const K
 #pragma unroll
             for (int w = 0; w < 16; ++w) t2 += s16 + w < K.nsplit ? pv[w] : 0.0;
           }
-          const float kv = (float)((double)K.scale * exp(-t2 / (double)K.h));
+          float kv;
+          if constexpr (DIST) kv = (float)t2;
+          else kv = (float)((double)K.scale * exp(-t2 / (double)K.h));
           const bool mirror = K.symmetric && Ucur.b0 > Ucur.a0;
           K.kout[(size_t)a * K.M + b] = kv;
           if (mirror) K.kout[(size_t)b * K.M + a] = kv;
@@ -267,15 +271,16 @@ __device__ __forceinline__ void kmat_tile_loop(float* __restrict__ smem, const K
     __syncthreads();
   }
 }
+template <bool DIST = false>
 __device__ __forceinline__ void kmat_tile_block(float* __restrict__ smem, const KmatTile& K, int first, int step, int tid) {
   const int units = kmat_tile_count(K.nta, K.ntb, K.symmetric) * K.nsplit;
   if (first >= units) return;
   // (two copies of the loop: merged, the compiler shares the tails of the two fetch batches and waits on every load)
   const bool vec = (((K.stride | K.off | (size_t)K.len) & 3) == 0) && ((reinterpret_cast<uintptr_t>(K.x) & 15) == 0);
   if (vec)
-    kmat_tile_loop<true>(smem, K, first, step, units, tid);
+    kmat_tile_loop<true, DIST>(smem, K, first, step, units, tid);
   else
-    kmat_tile_loop<false>(smem, K, first, step, units, tid);
+    kmat_tile_loop<false, DIST>(smem, K, first, step, units, tid);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -454,6 +459,9 @@ __device__ __forceinline__ void kmat_finish_row(const double* __restrict__ part,
 //     reference: kernel.py:20-30 / 52-71, svgd.py:165-176 / 537-551
 // grid = Mloc, block = 256; dynamic LDS = len * 4
 // ------------------------------------------------------------------------------------------------
+// DIST (the distance pass of the median-heuristic bandwidth): the epilogue stores (float)tot, the sum of squared
+// differences itself, in place of scale * exp(-tot / h) -- the same tot, so what the bandwidth is selected from is what the matrix uses
+template <bool DIST = false>
 __device__ __forceinline__ void kmat_block(float* __restrict__ smem, const float* __restrict__ pack, size_t pack_stride,
                                            size_t seg_off, int len, float* __restrict__ kout, int m0, int M, float scale, float h,
                                            int symmetric, int a, int bt, const float* __restrict__ kadd = nullptr,
@@ -546,7 +554,9 @@ __device__ __forceinline__ void kmat_block(float* __restrict__ smem, const float
     if (b >= M) continue;
     const double tot = wave_sum_d(acc[q]);
     if (lane == 0) {
-      const float kv = (float)((double)scale * exp(-tot / (double)h));
+      float kv;
+      if constexpr (DIST) kv = (float)tot;
+      else kv = (float)((double)scale * exp(-tot / (double)h));
       kout[(size_t)a * M + b] = kv;
       if (symmetric && b > a) kout[(size_t)b * M + a] = kv;
       if (ksum) {

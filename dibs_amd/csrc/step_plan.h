@@ -29,6 +29,8 @@ struct StepFacts {
   int terms;                  // TERMS_*
   int kmat_tiled_min;         // DibsTuning
   bool no_kmat_fuse, no_kmat_grad;
+  bool median_h = false;      // a kernel bandwidth comes from the median rule (dibs_config.reserved_i[3]): selected on the device in front
+                              // of the kernel matrices, which are then launches of their own (no fused placement, no external slab)
 };
 
 // Exactly one place computes a step's kernel matrices:
@@ -115,6 +117,14 @@ static inline StepPlan plan_step(const StepFacts& f) {
   // ---- the kernel matrices ----
   // A sharded rank (Mloc != M) has only its own particles in phase A: phase B computes its slab from the gathered rows, or the caller's
   // side stream has done so from the gathered values (External).  The same holds with explicit keys (nothing moves: no phase B follows).
+  // Median-rule bandwidth (median_h): distance pass -> selection -> kernel matrices, in that order on one stream.  The fused placements
+  // (InSample, InTail) carry a bandwidth as a launch argument of a kernel that starts before the selection could have run, and an External
+  // slab was computed without one, so neither is chosen: the second stream where the step forks, phase B otherwise.  Fork and join are
+  // what they are without the flag.  (dibs_engine_create admits the rule on one rank only and refuses dibs_engine_kmat_values.)
+  if (f.median_h) {
+    if (fork && !f.xk && single_rank) p.place = KmatPlace::Stream2;
+    return p;
+  }
   if (f.kmat_ext) {
     p.place = KmatPlace::External;
     return p;

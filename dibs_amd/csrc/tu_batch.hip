@@ -10,6 +10,7 @@
 #include "kernels_acyc.h"
 #include "kernels_acyc_bf16.h"
 #include "kernels_acyc_f16.h"
+#include "bandwidth_select.h"
 
 // batched engines (include/dibs_hip.h, per-problem hyper-parameters): the same block with alpha of the particle's problem, row m / pM of
 // the table (block-uniform: a scalar load); no fork flag
@@ -189,4 +190,111 @@ void chains_launch_kmat_hp(hipStream_t st, bool tiled, const float* x, size_t le
   dibs_allow_lds((const void*)k_kmat_chains_hp, lds_direct);
   hipLaunchKernelGGL(k_kmat_chains_hp, dim3((unsigned)(C * M), (unsigned)((M + KMAT_BT - 1) / KMAT_BT)), dim3(256), lds_direct, st, x, len, (int)len, kout, M,
                      scale, hp, theta_seg, kadd, ksum);
+}
+
+// ---- median-heuristic kernel bandwidth (dibs_config.reserved_i[3]) -----------------------------------------------
+// Per run (a standalone engine's particles, a problem, a chain) and segment (z, theta): h = median ||x_a - x_b||^2 / log(M + 1), selected on
+// the device in front of the kernel matrices of every step.  Three launches on one stream: the distance pass below, the selection, then the
+// table-reading kernel matrices above (the batched engine's: kernels_marginal.h), which find the bandwidth in the run's row of ProblemHP.
+//
+// 1. distance pass: the block functions of the kernel matrices with the DIST epilogue -- out [C * M][M] holds (float)tot of every pair, the
+//    very sums the matrices form again behind the selection (same code, same grids: symmetric, zero diagonal).  Grids and LDS as
+//    k_kmat_chains / k_kmat_tile_chains.
+__global__ __launch_bounds__(256) void k_sqdist_chains(const float* __restrict__ x, size_t stride, int len, float* __restrict__ out, int M) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int a = blockIdx.x, p = a / M;
+  kmat_block<true>(smem, x + (size_t)p * M * stride, stride, 0, len, out + (size_t)p * M * M, 0, M, 0.f, 0.f, 1, a - p * M, blockIdx.y);
+}
+__global__ __launch_bounds__(KT_NT) void k_sqdist_tile_chains(KmatTile kt) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const size_t p = blockIdx.y;
+  KmatTile k = kt;
+  k.x = kt.x + p * (size_t)kt.M * kt.stride;
+  k.kout = kt.kout + p * (size_t)kt.M * kt.M;
+  kmat_tile_block<true>(smem, k, (int)blockIdx.x, (int)gridDim.x, (int)threadIdx.x);
+}
+void bandwidth_launch_sqdist(hipStream_t st, bool tiled, const float* x, size_t len, float* out, int C, int M, size_t lds_direct) {
+  if (tiled) {
+    const int nta = (M + KT_T - 1) / KT_T, tiles = kmat_tile_count(nta, nta, 1), nchunk = kmat_nchunk((int)len);
+    const KmatTile kt{x, len, 0, (int)len, nullptr, 0, M, M, nchunk, nta, nta, 1, 1, nchunk, 0.f, 0.f, out, nullptr, nullptr, nullptr};
+    dibs_allow_lds((const void*)k_sqdist_tile_chains, kmat_tile_lds_bytes());
+    hipLaunchKernelGGL(k_sqdist_tile_chains, dim3((unsigned)tiles, (unsigned)C), dim3(KT_NT), kmat_tile_lds_bytes(), st, kt);
+    return;
+  }
+  dibs_allow_lds((const void*)k_sqdist_chains, lds_direct);
+  hipLaunchKernelGGL(k_sqdist_chains, dim3((unsigned)(C * M), (unsigned)((M + KMAT_BT - 1) / KMAT_BT)), dim3(256), lds_direct, st, x, len, (int)len, out, M);
+}
+
+// 2. selection: one block per (run, segment on the median rule).  An exact radix select (bandwidth_select.h) on the bit patterns of the
+//    P = M (M - 1) / 2 entries above the diagonal of the run's [M][M] block: four passes of one 8-bit digit each, most significant first,
+//    for the two order statistics of the median at once (one histogram each; an odd P asks for the same one twice).  A pass counts with
+//    integer LDS atomics only, so the result is the same whatever order the threads arrive in.  The values are RE-READ from the distance
+//    buffer in every pass instead of being held in LDS: at most 255^2 floats = 254 KiB that the distance pass has just left in the L2,
+//    read four times by 1 024 threads with coalesced loads, against 127 KiB of dynamic LDS that would keep the block off every CU on which
+//    an acyclicity or estimator block of the other stream is resident -- this way the block needs 2 KiB.  Squared distances share their
+//    leading digits (one or two exponents), so a thread merges runs of equal digits before it touches the histogram: the first passes
+//    would otherwise be 32 000 atomics on one LDS word.  Wave w sweeps the rows w, w + 16, ... of the upper triangle, a lane the columns
+//    a + 1 + lane, + 64, ...: contiguous loads, no division, and every loop bound a function of M (and the row) alone.  The walk from the
+//    histogram to the digit is two levels of 16 (bw_walk): 16 threads per order statistic sum a group of bins each, one thread walks.
+//    Thread 0 writes the bandwidth to the run's row of the table (h or h_theta) and to bw [C][2] (DIBS_BUF_BANDWIDTH).
+__global__ __launch_bounds__(1024) void k_bandwidth_median(const float* __restrict__ sqd_z, const float* __restrict__ sqd_t, int seg_a, int seg_b,
+                                                           int M, double inv_log, ProblemHP* __restrict__ hp, float* __restrict__ bw) {
+  __shared__ uint32_t hist[2][BW_BINS];
+  __shared__ uint32_t grp[2][BW_NGROUPS];
+  __shared__ uint32_t sel[2][2];  // per order statistic: the digits chosen so far, the rank still wanted
+  const int run = blockIdx.x, seg = blockIdx.y ? seg_b : seg_a, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t* __restrict__ v = reinterpret_cast<const uint32_t*>((seg ? sqd_t : sqd_z) + (size_t)run * M * M);
+  const uint32_t P = (uint32_t)M * (uint32_t)(M - 1) / 2u;
+  const BwRanks want = bw_median_ranks(P);
+  uint32_t pre[2] = {0u, 0u}, rank[2] = {want.lo, want.hi};
+  for (int pass = 0; pass < BW_PASSES; ++pass) {
+    for (int i = tid; i < 2 * BW_BINS; i += 1024) (&hist[0][0])[i] = 0u;
+    __syncthreads();
+    const uint32_t mask = bw_prefix_mask(pass);
+    uint32_t last[2] = {0u, 0u}, cnt[2] = {0u, 0u};  // a thread's current run of equal digits
+    for (int a = wave; a < M - 1; a += 16) {
+      const uint32_t* __restrict__ row = v + (size_t)a * M;
+      for (int b = a + 1 + lane; b < M; b += 64) {
+        const uint32_t bits = row[b], dg = bw_digit(bits, pass);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          if ((bits & mask) == pre[j]) {
+            if (dg != last[j] && cnt[j]) {
+              atomicAdd(&hist[j][last[j]], cnt[j]);
+              cnt[j] = 0u;
+            }
+            last[j] = dg;
+            ++cnt[j];
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+      if (cnt[j]) atomicAdd(&hist[j][last[j]], cnt[j]);
+    __syncthreads();
+    if (tid < 2 * BW_NGROUPS) grp[tid / BW_NGROUPS][tid % BW_NGROUPS] = bw_group_sum(hist[tid / BW_NGROUPS], tid % BW_NGROUPS);
+    __syncthreads();
+    if (tid == 0 || tid == 64) {  // (one wave per order statistic)
+      const int j = tid >> 6;
+      const BwStep s = bw_walk(hist[j], grp[j], rank[j]);
+      sel[j][0] = pre[j] | (s.bin << (24 - 8 * pass));
+      sel[j][1] = s.rank;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 2; ++j) pre[j] = sel[j][0], rank[j] = sel[j][1];
+  }
+  if (tid == 0) {
+    const float h = bw_from_median(bw_median(bw_bits_to_float(pre[0]), bw_bits_to_float(pre[1]), P), inv_log);
+    if (seg) hp[run].h_theta = h;
+    else hp[run].h = h;
+    bw[2 * run + seg] = h;
+  }
+}
+// rule: bit 0 the latent segment, bit 1 theta (dibs_config.reserved_i[3]); M >= 2
+void bandwidth_launch_select(hipStream_t st, const float* sqd_z, const float* sqd_t, int rule, int C, int M, ProblemHP* hp, float* bw) {
+  const int nseg = (rule & 1) + ((rule >> 1) & 1), seg_a = (rule & 1) ? 0 : 1;
+  if (!nseg) return;
+  hipLaunchKernelGGL(k_bandwidth_median, dim3((unsigned)C, (unsigned)nseg), dim3(1024), 0, st, sqd_z, sqd_t, seg_a, 1, M, 1.0 / log((double)(M + 1)), hp, bw);
 }

@@ -255,6 +255,8 @@ class Engine:
 
     def read(self, name):
         nbytes = int(self.lib.dibs_engine_buffer_bytes(self._h, BUF[name]))
+        if nbytes == -2:   # (a buffer this engine's configuration does not have: the C side says which and why)
+            _lib.check(self.lib.dibs_engine_read_buffer(self._h, BUF[name], _ptr(np.empty(1, np.float32)), 4))
         if nbytes < 0:
             raise KeyError(name)
         dt = np.float64 if (self.precision == 64 and name in _F64_BUFS) else _BUF_DTYPE.get(name, np.float32)

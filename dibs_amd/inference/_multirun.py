@@ -35,6 +35,8 @@ def _shared_fields(cfg):
         out[name] = tuple(v) if hasattr(v, "__len__") else v
     if out["latent_prior_std"] <= 0:  # (unset: the default filled in)
         out["latent_prior_std"] = default_latent_prior_std(cfg.n_dim)
+    # reserved_i is per run but for its slot 3: which kernels take the median-rule bandwidth is one setting of the engine
+    out["kernel bandwidth rule"] = int(cfg.reserved_i[3])
     return out
 
 
@@ -152,6 +154,8 @@ def _run(Engine, cfg, kind, models, keys, data, edge_probs, hparams, *, n_partic
                 for m, s in zip(models, per_run(eng.get_state())):
                     callback(dibs=m, t=t + n, zs=s["z"], **(dict(thetas=m._theta_out(s["theta"])) if joint else {}))
         st = eng.get_state()
+        for m, bw in zip(models, eng.read("BANDWIDTH").reshape(B, 2)):
+            m.last_bandwidth = bw.copy()   # (as sample() leaves it; one model object in several runs keeps the last run's)
     finally:
         eng.close()
     return [{name: None if a is None else a.copy() for name, a in s.items()} for s in per_run(st)]

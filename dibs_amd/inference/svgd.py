@@ -193,6 +193,9 @@ class _SVGDBase(DiBS):
                         kw["thetas"] = self._theta_out(st["theta"])
                     callback(**kw)
             st = eng.get_state()
+            if self.precision == "float32":
+                # (h_latent, h_theta) the last step's kernel matrices used: the configured values, or what the median rule selected
+                self.last_bandwidth = eng.read("BANDWIDTH").reshape(2).copy()
         finally:
             eng.close()
             self._engine = None

@@ -59,7 +59,9 @@ typedef struct dibs_config {
   int32_t device_id;
   int32_t reserved_i[5];    /* [0] n_problems: 0 / 1 = one problem; B > 1 = a batched engine (see dibs_engine_set_data_problem)
                                [1] precision: 0 / 32 = float32, 64 = the float64 engine (see dibs_engine_set_data_f64)
-                               [2] n_chains: 0 / 1 = one chain (the standalone engine); C > 1 = a chains engine (see CHAINS ENGINE) */
+                               [2] n_chains: 0 / 1 = one chain (the standalone engine); C > 1 = a chains engine (see CHAINS ENGINE)
+                               [3] bandwidth rule: 0 = h_latent / h_theta as given; bit 0: the latent kernel's bandwidth, bit 1: the
+                                   parameter kernel's (joint models) by the median heuristic (see MEDIAN-HEURISTIC KERNEL BANDWIDTH) */
 
   double alpha_linear;      /* dibs.py:70 */
   double beta_linear;       /* dibs.py:71 */
@@ -106,6 +108,11 @@ enum {
   DIBS_BUF_PHI_THETA = 16,
   DIBS_BUF_GATHER = 17,    /* f32 packed all-gather payload        */
   DIBS_BUF_PROBLEM_STEP = 18, /* f32 [B, 2]  batched engines: (alpha, beta) of the last step as the device formed them per problem */
+  DIBS_BUF_BANDWIDTH = 19,    /* f32 [B, 2]  (h_latent, h_theta) the last step's kernel matrices used, per run (B = 1: the standalone engine).
+                                 Fixed rule: the configuration's (or the run's own) values; see MEDIAN-HEURISTIC KERNEL BANDWIDTH */
+  DIBS_BUF_SQDIST_Z = 20,     /* f32 [B * M, M]  squared distances ||z_a - z_b||^2 the selection of the last step saw, per run: symmetric, zero
+                                 diagonal.  Only while the latent kernel is on the median rule ("no such buffer" otherwise)               */
+  DIBS_BUF_SQDIST_THETA = 21, /* f32 [B * M, M]  the same for theta (parameter kernel on the median rule)                                */
   DIBS_BUF_COUNT
 };
 
@@ -114,6 +121,7 @@ enum {
   DIBS_K_EDGE = 0, DIBS_K_BGE_NODES = 1, DIBS_K_LIK_WEIGHTS = 2, DIBS_K_ACYC = 3, DIBS_K_ZGRAD = 4,
   DIBS_K_KMAT = 5, DIBS_K_PHI_UPDATE = 6, DIBS_K_LIN_THETA = 7, DIBS_K_LIN_Z = 8, DIBS_K_NN_THETA = 9,
   DIBS_K_NN_Z = 10, DIBS_K_PACK = 11, DIBS_K_BGE_BIG = 12 /* the three queue launches */, DIBS_K_ACYC_REDUCE = 13 /* k_acyc_reduce */, DIBS_K_TAIL = 14 /* k_particle_grad */,
+  DIBS_K_BANDWIDTH = 15 /* median-rule bandwidth: distance pass + k_bandwidth_median */,
   DIBS_K_COUNT = 16
 };
 
@@ -366,6 +374,23 @@ int dibs_engine_precision(const dibs_engine* e);
  * creation and a chains engine with per-chain hyper-parameters that differ refuses it when the particles are initialised: the
  * table-reading kernels of those tiers have no edge-wise form, and per-problem tables are not built. */
 int dibs_engine_set_edge_prior(dibs_engine* e, const double* edge_probs);
+
+/* MEDIAN-HEURISTIC KERNEL BANDWIDTH (no reference counterpart: the reference's kernels take fixed h; the rule is Liu & Wang 2016).
+ * dibs_config.reserved_i[3] != 0 makes the engine select a kernel's bandwidth on the device in every step, per RUN (the M particles of a
+ * standalone engine, of one problem of a batched engine, of one chain) and per SEGMENT (bit 0: latent z, bit 1: parameters theta):
+ *   v_ab = (float)tot_ab, tot_ab the double sum of squared differences the kernel-matrix code forms for the pair (a, b) before its exp;
+ *   med  = median of the P = M (M - 1) / 2 values v_ab, a < b: P odd the order statistic (P - 1) / 2, P even 0.5f * (v[P/2 - 1] + v[P/2]);
+ *   h    = max((float)((double)med * (1 / log((double)(M + 1)))), FLT_MIN)    (the floor: more than half of the pairs identical)
+ * and the kernel matrix is what it always is, (float)(scale * exp(-tot_ab / (double)h)).  The selection is exact (a radix select on the bit
+ * patterns, integer counting) and so bit-reproducible; non-finite distances give an unspecified but deterministic h.  h_latent / h_theta
+ * of a segment on the rule are not read.  A step with the rule equals, bit for bit, the step of a fixed-rule engine configured with the
+ * float values DIBS_BUF_BANDWIDTH reports for it.  The kernel matrices are then launches of their own behind the selection (distance
+ * pass -> selection -> kernel matrices on one stream; none of the fused placements of the fixed rule), also in dibs_engine_step_local /
+ * dibs_engine_step_update of a single rank.  Batched and chains engines take the rule as they take per-run bandwidths: run i stays
+ * bit-identical to the standalone engine.  With reserved_i[3] == 0 the engine is launch for launch what it was.
+ * Limits, each an error of dibs_engine_create that starts "median bandwidth: ": n_particles (per run) >= 256 (the GEMM form of the SVGD
+ * transform has no table-reading form and the selection is one block per run: the follow-up), n_particles < 2, n_ranks > 1, the float64
+ * engine, bit 1 on a marginal model, a rule outside 0 .. 3; dibs_engine_kmat_values on such an engine fails the same way. */
 
 /* debugging / parity: copy a device buffer to the host (nbytes must match); theta size query */
 int dibs_engine_read_buffer(dibs_engine* e, int32_t which, void* host, int64_t nbytes);
