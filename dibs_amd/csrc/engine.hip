@@ -84,26 +84,11 @@ static int engine_alloc(dibs_engine* e, const dibs_config& c, void* stream) {
     }
   }
   e->acyc_nt = e->dpad / 16;
-  {  // chains per block: fill the 256 CUs in whole rounds (resident blocks per CU limited by the 3 LDS matrices)
-    const size_t lds = (size_t)(3 * e->dpad + 1) * (e->dpad + 4) * 4;
-    const int per_cu = (int)(LDS_LIMIT / lds) < 1 ? 1 : (int)(LDS_LIMIT / lds);
-    const int slots = 256 * (per_cu > 8 ? 8 : per_cu);
-    // a work unit is a PAIR of chains when the PRNG layout lets one Threefry call serve both (see k_acyc), else one chain
-    const bool paired = c.rng_layout == DIBS_RNG_LEGACY && (e->Sa & 1) == 0 && (uint64_t)e->Sa * e->d * e->d < 0xFFFFFFFFull;
-    const int n_units = paired ? e->Sa / 2 : e->Sa;
-    e->acyc_units = n_units;
-    int best = 1;
-    long best_cost = -1;
-    for (int cpb = 1; cpb <= n_units; ++cpb) {
-      // (sized for the GLOBAL particle count: the grouping of the Sa chains into partial sums must not depend on how the
-      //  particles are sharded, or results would differ between rank counts in the last float bit)
-      const long nblk = (long)((n_units + cpb - 1) / cpb) * e->M;
-      const long cost = ((nblk + slots - 1) / slots) * cpb;
-      if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = cpb; }
-    }
-    e->acyc_cpb = best;
-  }
-  e->acyc_nblk = (e->acyc_units + e->acyc_cpb - 1) / e->acyc_cpb;
+  // One acyclicity block per work unit: a PAIR of chains when the PRNG layout lets one Threefry call serve both (see k_acyc), else one
+  // chain.  (The grouping of the Sa chains into partial sums depends on Sa, d and the layout alone -- not on the particle count or how
+  //  the particles are sharded, so results do not differ between rank counts in the last float bit.)
+  e->acyc_paired = c.rng_layout == DIBS_RNG_LEGACY && (e->Sa & 1) == 0 && (uint64_t)e->Sa * e->d * e->d < 0xFFFFFFFFull;
+  e->acyc_units = e->acyc_paired ? e->Sa / 2 : e->Sa;
   e->sigz = latent_sigma(c.latent_prior_std, e->k);
   if (stream) {
     e->stream = (hipStream_t)stream;
@@ -192,7 +177,7 @@ static int engine_alloc(dibs_engine* e, const dibs_config& c, void* stream) {
                   std::to_string(acyc_big_elems(e->Mloc, e->d, e->Sa) * 4 >> 20) + " MiB failed");
     }
   } else {
-    HIP_OK(dalloc(&e->acyc_part, Ml * e->acyc_nblk * dd));
+    HIP_OK(dalloc(&e->acyc_part, Ml * e->acyc_units * dd));
   }
   HIP_OK(dalloc(&e->w_acyc, Ml * dd));
   {

@@ -119,7 +119,8 @@ struct dibs_engine {
     double alpha_lambd = 0;
   } bst;
   int64_t D, P, E, Ev;  // z elems / theta elems per particle, packed row stride [z | grad_z | theta | grad_theta], plane row stride [z | theta] (floats)
-  int dpad, ldk, edge_kc, acyc_nt, acyc_cpb, acyc_nblk, acyc_units;
+  int dpad, ldk, edge_kc, acyc_nt, acyc_units;  // acyc_units: acyclicity blocks per particle (engine_alloc)
+  bool acyc_paired;                             // ... each a Threefry pair of chains (else a single chain)
   float sigz;
   hipStream_t stream;
   bool own_stream;

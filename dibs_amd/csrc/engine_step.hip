@@ -134,8 +134,8 @@ static void kmat_launch_tiled(dibs_engine* e, hipStream_t st, const float* x, si
 // the matrix powers of the acyclicity term and their reduction on `st`, keys from `carry` (Mg: see step_local)
 static void launch_acyc(dibs_engine* e, hipStream_t st, Key2 carry, int Mg, float alpha) {
   const dibs_config& c = e->cfg;
-  const AcycLaunch al{st, e->scores, e->acyc_part, e->w_acyc, e->acyc_big, carry, e->m0, Mg, e->Mloc, e->d, e->Sa, e->acyc_cpb, e->acyc_units,
-                      e->acyc_nblk, alpha, (float)c.tau, c.rng_layout, c.logistic_minval_tiny, nullptr, nullptr, e->eas, e->tune.acyc_pipe,
+  const AcycLaunch al{st, e->scores, e->acyc_part, e->w_acyc, e->acyc_big, carry, e->m0, Mg, e->Mloc, e->d, e->Sa, e->acyc_units,
+                      e->acyc_paired, alpha, (float)c.tau, c.rng_layout, c.logistic_minval_tiny, nullptr, nullptr, e->eas, e->tune.acyc_pipe,
                       e->tune.acyc_hfw_max};
   acyc_power_timed(e, al, st);
   KTimer tm(e, DIBS_K_ACYC_REDUCE, st);
@@ -620,7 +620,7 @@ int carry_copy(dibs_engine* e, bool restore) {
 // keys (Mg = -1, rng_explicit_row) that the keys kernel derives from the B device-resident carries; the kernel matrices are block-diagonal
 // [B * M][M] and phi sums over a run's own block (k_phi_update's BATCH forms, grid.y = run).  Fork / join of the second stream by events
 // only (no flags), the kernel matrices standalone on the second stream (no fusions).  Every choice a standalone engine makes from its
-// particle count is made from M, one run's (acyc_cpb, the kernel-matrix algorithm, phi's TA / FULL, JointLaunch::M_choice), never from B * M.
+// particle count is made from M, one run's (the kernel-matrix algorithm, phi's TA / FULL, JointLaunch::M_choice), never from B * M.
 // The two kinds differ where step_local branches between the BGe score estimator and a joint model:
 //  * batched: B independent MarginalDiBS + BGe problems, each with its own data.  The BGe kernels look up problem m / M's statistics (BATCH
 //    instantiations); one kernel matrix (latent).
@@ -645,8 +645,8 @@ static void batch_edge_scores(dibs_engine* e) {
 }
 static void batch_acyc(dibs_engine* e, hipStream_t st, Key2 carry) {
   const dibs_config& c = e->cfg;
-  const AcycLaunch al{st, e->scores, e->acyc_part, e->w_acyc, nullptr, carry, 0, -1, e->Mloc, e->d, e->Sa, e->acyc_cpb, e->acyc_units,
-                      e->acyc_nblk, 0.f, (float)c.tau, c.rng_layout, c.logistic_minval_tiny, nullptr, nullptr, e->eas, e->tune.acyc_pipe,
+  const AcycLaunch al{st, e->scores, e->acyc_part, e->w_acyc, nullptr, carry, 0, -1, e->Mloc, e->d, e->Sa, e->acyc_units,
+                      e->acyc_paired, 0.f, (float)c.tau, c.rng_layout, c.logistic_minval_tiny, nullptr, nullptr, e->eas, e->tune.acyc_pipe,
                       e->tune.acyc_hfw_max};
   {
     KTimer tm(e, DIBS_K_ACYC, st);

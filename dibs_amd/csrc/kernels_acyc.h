@@ -5,9 +5,10 @@
 // ------------------------------------------------------------------------------------------------
 // K5  acyclicity gradient: for Gumbel-soft graphs G~ = sigmoid(tau (eps + alpha s)), M = I + G~/d,
 //     dh/dG~ = (M^{d-1})^T (h = tr(M^d) - d), chained through G~.  Matrix powers on f32 MFMA, all operands
-//     resident in LDS.  Each block handles CPB chains of one particle and writes their SUM; k_acyc_reduce adds the partial sums.
+//     resident in LDS.  Each block handles ONE unit of one particle -- a Threefry pair of chains (PAIRED), else a single chain -- and
+//     writes the unit's sum; k_acyc_reduce adds the partial sums.
 //     reference: graph_utils.py:8-28, dibs.py:121-140, 557-601
-// grid = (ceil(Sa / CPB), Mloc), block = 256; dynamic LDS = 3 * DP * LD * 4, DP = 16 NT, LD = DP + 2
+// grid = (units, Mloc), units = Sa / 2 (PAIRED) or Sa, block = 256; dynamic LDS = 3 * DP * LD * 4, DP = 16 NT, LD = DP + 2
 //
 // Serves d <= 32, and up to d = 112 the chains that cannot be paired (odd Sa) and DIBS_ACYC_F32=1 runs; 33 <= d <= 112 with paired chains
 // runs on kernels_acyc_f16.h by default (tu_acyc.hip; DIBS_ACYC_BF16=1: kernels_acyc_bf16.h).  At the headline size
@@ -167,11 +168,13 @@ __device__ __forceinline__ void acyc_matmul(float* __restrict__ lds, int c_off, 
 
 template <int NT, bool PAIRED>
 __device__ __forceinline__ void acyc_block(const float* __restrict__ scores, float* __restrict__ part, Key2 carry, int m0,
-                                           int M_global, int d, int Sa, int cpb, float alpha, float tau, int layout,
-                                           int tiny, int n_acyc_blk) {
+                                           int M_global, int d, int Sa, float alpha, float tau, int layout, int tiny) {
   constexpr int DP = 16 * NT, LD = DP + 4, BUF = DP * LD;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int blk = blockIdx.x, m = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int unit = blockIdx.x, m = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // padding of buffer 0: zeroed once, never written afterwards.  (First thing in the kernel: placed behind the key set-up, right in front of
+  //  the chains, k_acyc<5, true> takes 260 registers instead of 246 and loses its second wave per SIMD.)
+  for (int e = tid; e < BUF; e += 256) smem[e] = 0.f;
   const Key2 km = rng_split_row_uniform(carry, (uint32_t)M_global + 1u, (uint32_t)(m0 + m) + 1u, layout);  // dibs.py:595: key used directly
   const uint64_t dd = (uint64_t)d * d, nbits = (uint64_t)Sa * dd;
   const int kp = (d + 3) & ~3;
@@ -202,87 +205,82 @@ __device__ __forceinline__ void acyc_block(const float* __restrict__ scores, flo
     out[q] = 0.f;
     gnext[q] = 0.f;
   }
-  for (int e = tid; e < BUF; e += 256) smem[e] = 0.f;  // padding of buffer 0: zeroed once, never written afterwards
 
-  for (int c = 0; c < cpb; ++c) {
-    const int unit = blk * cpb + c;
-    if (unit >= n_units) break;
-    for (int hf = 0; hf < (paired ? 2 : 1); ++hf) {
-      const int sa = paired ? unit + hf * (Sa >> 1) : unit;
-      const float* sml = sm;
-      asm volatile("" : "+s"(sml));  // opaque per pass: otherwise exp(-alpha s) is hoisted out of the loops into EPT live VGPRs
-      __syncthreads();
-      // buffer 0: M = I + G~/d  (permuted columns)
+  for (int hf = 0; hf < (paired ? 2 : 1); ++hf) {
+    const int sa = paired ? unit + hf * (Sa >> 1) : unit;
+    const float* sml = sm;
+    asm volatile("" : "+s"(sml));  // opaque per pass: otherwise exp(-alpha s) is hoisted out of the loops into EPT live VGPRs
+    __syncthreads();
+    // buffer 0: M = I + G~/d  (permuted columns)
 #pragma unroll
-      for (int q = 0; q < EPT; ++q) {
-        const int i = pi0 + q * R;
-        if (pact && i < d) {
-          float v = 1.0f;
-          if (i != pj) {
-            float g;
-            if (paired && hf == 1) {
-              g = gnext[q];
+    for (int q = 0; q < EPT; ++q) {
+      const int i = pi0 + q * R;
+      if (pact && i < d) {
+        float v = 1.0f;
+        if (i != pj) {
+          float g;
+          if (paired && hf == 1) {
+            g = gnext[q];
+          } else {
+            const float as = alpha * sml[i * d + pj];
+            const float ea = fast ? expf(-as) : as;
+            uint32_t y0, y1 = 0u;
+            if (paired) {
+              // counter sa d d + i d + pj, i = pi0 + q R: the lane's part is pi0 d + pj
+              threefry2x32_uh(tk, (uint32_t)(pi0 * d + pj), (uint32_t)((uint64_t)sa * dd) + (uint32_t)(q * R * d), (uint32_t)(nbits >> 1), y0, y1);
             } else {
-              const float as = alpha * sml[i * d + pj];
-              const float ea = fast ? expf(-as) : as;
-              uint32_t y0, y1 = 0u;
-              if (paired) {
-                // counter sa d d + i d + pj, i = pi0 + q R: the lane's part is pi0 d + pj
-                threefry2x32_uh(tk, (uint32_t)(pi0 * d + pj), (uint32_t)((uint64_t)sa * dd) + (uint32_t)(q * R * d), (uint32_t)(nbits >> 1), y0, y1);
-              } else {
-                y0 = rng_bits_at(km, nbits, (uint64_t)sa * dd + (uint64_t)(i * d + pj), layout);
-              }
-              if (fast) {
-                const float u0 = rng_uniform(y0, ulo, 1.0f), u1 = rng_uniform(y1, ulo, 1.0f);
-                // (v_rcp_f32, 1 ulp: the IEEE division sequence is ten instructions per draw, and this kernel's time is the SUM of its
-                //  MFMA and VALU issue cycles)
-                // saturated edges (exp(-alpha s) below the rounding of the denominator) give exactly 1, as the reference's sigmoid does
-                const float den0 = fmaf(1.0f - u0, ea, u0), den1 = fmaf(1.0f - u1, ea, u1);
-                g = den0 == u0 ? 1.0f : u0 * __builtin_amdgcn_rcpf(den0);
-                gnext[q] = den1 == u1 ? 1.0f : u1 * __builtin_amdgcn_rcpf(den1);
-              } else {
-                g = 1.0f / (1.0f + expf(-tau * (rng_logistic(y0, tiny) + ea)));
-                gnext[q] = 1.0f / (1.0f + expf(-tau * (rng_logistic(y1, tiny) + ea)));
-              }
+              y0 = rng_bits_at(km, nbits, (uint64_t)sa * dd + (uint64_t)(i * d + pj), layout);
             }
-            v = g * inv_d;
+            if (fast) {
+              const float u0 = rng_uniform(y0, ulo, 1.0f), u1 = rng_uniform(y1, ulo, 1.0f);
+              // (v_rcp_f32, 1 ulp: the IEEE division sequence is ten instructions per draw, and this kernel's time is the SUM of its
+              //  MFMA and VALU issue cycles)
+              // saturated edges (exp(-alpha s) below the rounding of the denominator) give exactly 1, as the reference's sigmoid does
+              const float den0 = fmaf(1.0f - u0, ea, u0), den1 = fmaf(1.0f - u1, ea, u1);
+              g = den0 == u0 ? 1.0f : u0 * __builtin_amdgcn_rcpf(den0);
+              gnext[q] = den1 == u1 ? 1.0f : u1 * __builtin_amdgcn_rcpf(den1);
+            } else {
+              g = 1.0f / (1.0f + expf(-tau * (rng_logistic(y0, tiny) + ea)));
+              gnext[q] = 1.0f / (1.0f + expf(-tau * (rng_logistic(y1, tiny) + ea)));
+            }
           }
-          smem[i * LD + pcj] = v;
+          v = g * inv_d;
         }
+        smem[i * LD + pcj] = v;
       }
-      __syncthreads();
-      // left-to-right binary powering of e = d - 1; the running power ping-pongs between buffers 1 and 2
-      const int ex = d - 1;
-      int cur = 0;
-      if (ex >= 1) {
-        const int hb = 31 - __builtin_clz((unsigned)ex);
-        for (int b = hb - 1; b >= 0; --b) {
-          int dst = (cur == BUF) ? 2 * BUF : BUF;
-          acyc_matmul<NT>(smem, dst, cur, cur, kp >> 2, lane, wave);
+    }
+    __syncthreads();
+    // left-to-right binary powering of e = d - 1; the running power ping-pongs between buffers 1 and 2
+    const int ex = d - 1;
+    int cur = 0;
+    if (ex >= 1) {
+      const int hb = 31 - __builtin_clz((unsigned)ex);
+      for (int b = hb - 1; b >= 0; --b) {
+        int dst = (cur == BUF) ? 2 * BUF : BUF;
+        acyc_matmul<NT>(smem, dst, cur, cur, kp >> 2, lane, wave);
+        __syncthreads();
+        cur = dst;
+        if ((ex >> b) & 1) {
+          dst = (cur == BUF) ? 2 * BUF : BUF;
+          acyc_matmul<NT>(smem, dst, cur, 0, kp >> 2, lane, wave);
           __syncthreads();
           cur = dst;
-          if ((ex >> b) & 1) {
-            dst = (cur == BUF) ? 2 * BUF : BUF;
-            acyc_matmul<NT>(smem, dst, cur, 0, kp >> 2, lane, wave);
-            __syncthreads();
-            cur = dst;
-          }
         }
       }
-      // out[i][j] += (M^{d-1})[j][i] * tau * alpha * g (1 - g)   (i != j);  g = d * M[i][j] from buffer 0
+    }
+    // out[i][j] += (M^{d-1})[j][i] * tau * alpha * g (1 - g)   (i != j);  g = d * M[i][j] from buffer 0
 #pragma unroll
-      for (int q = 0; q < EPT; ++q) {
-        const int i = pi0 + q * R;
-        if (pact && i < d && i != pj) {
-          float g = smem[i * LD + pcj] * fd;
-          g = g > 0.99999988f ? 1.0f : g;  // (g / d) * d of a saturated edge may round to 1 - 2^-24 or 1 + 2^-23: g (1 - g) has to be 0 there
-          out[q] += smem[cur + pj * LD + acyc_pc<NT>(i)] * tau * alpha * g * (1.0f - g);
-        }
+    for (int q = 0; q < EPT; ++q) {
+      const int i = pi0 + q * R;
+      if (pact && i < d && i != pj) {
+        float g = smem[i * LD + pcj] * fd;
+        g = g > 0.99999988f ? 1.0f : g;  // (g / d) * d of a saturated edge may round to 1 - 2^-24 or 1 + 2^-23: g (1 - g) has to be 0 there
+        out[q] += smem[cur + pj * LD + acyc_pc<NT>(i)] * tau * alpha * g * (1.0f - g);
       }
     }
   }
   if (pact) {
-    float* po = part + ((size_t)m * n_acyc_blk + blk) * dd;
+    float* po = part + ((size_t)m * n_units + unit) * dd;
 #pragma unroll
     for (int q = 0; q < EPT; ++q) {
       const int i = pi0 + q * R;
@@ -292,15 +290,14 @@ __device__ __forceinline__ void acyc_block(const float* __restrict__ scores, flo
 }
 template <int NT, bool PAIRED>
 __global__ __launch_bounds__(256) void k_acyc(const float* __restrict__ scores, float* __restrict__ part, Key2 carry, int m0,
-                                              int M_global, int d, int Sa, int cpb, float alpha, float tau, int layout,
-                                              int tiny, int n_acyc_blk) {
-  acyc_block<NT, PAIRED>(scores, part, carry, m0, M_global, d, Sa, cpb, alpha, tau, layout, tiny, n_acyc_blk);
+                                              int M_global, int d, int Sa, float alpha, float tau, int layout, int tiny) {
+  acyc_block<NT, PAIRED>(scores, part, carry, m0, M_global, d, Sa, alpha, tau, layout, tiny);
 }
 // batched engines (include/dibs_hip.h, per-problem hyper-parameters): alpha of the block's particle from row m / pM of the table
 // (block-uniform: a scalar load)
 template <int NT, bool PAIRED>
 __global__ __launch_bounds__(256) void k_acyc_batch(const float* __restrict__ scores, float* __restrict__ part, Key2 carry, int m0,
-                                                    int M_global, int d, int Sa, int cpb, const ProblemHP* __restrict__ hp, int pM,
-                                                    float tau, int layout, int tiny, int n_acyc_blk) {
-  acyc_block<NT, PAIRED>(scores, part, carry, m0, M_global, d, Sa, cpb, hp[blockIdx.y / (unsigned)pM].alpha, tau, layout, tiny, n_acyc_blk);
+                                                    int M_global, int d, int Sa, const ProblemHP* __restrict__ hp, int pM, float tau, int layout,
+                                                    int tiny) {
+  acyc_block<NT, PAIRED>(scores, part, carry, m0, M_global, d, Sa, hp[blockIdx.y / (unsigned)pM].alpha, tau, layout, tiny);
 }

@@ -27,7 +27,7 @@
 // from the soft graph the thread drew itself -- M needs no image after the first squaring.
 // The last power is written as float [row][68] into the free image and read back transposed for
 //   out[a][b] += (M^{d-1})[b][a] * tau * alpha * g (1 - g).
-// grid = (ceil(Sa / 2 / cpb), Mloc rounded up to 8; re-indexed XCD-aware inside), block = 256,
+// grid = (Sa / 2, Mloc rounded up to 8; re-indexed XCD-aware inside: acyc_xcd_block), block = 256,
 // dynamic LDS = 2 * 24576
 //
 // Where the time goes at the headline size (2 048 blocks, 94 us; counters of scripts/probe/acyc_bf_probe.hip): 5.5 M MFMAs = 86 k cycles
@@ -165,20 +165,27 @@ __device__ __forceinline__ void abf_m0(const f32x4 (&g)[ABF_NT], f32x4 (&v)[ABF_
     }
 }
 
+// XCD-aware block order (grid = (units per particle, particles rounded up to 8)): workgroups go round-robin to the 8 XCDs in the
+// order of their linear id L; L = 8 (gridDim.x p_hi + u) + p_lo puts all units u of particle m = 8 p_hi + p_lo on XCD p_lo, so a
+// particle's score matrix is fetched into one L2 instead of all eight (17 MB of L2 misses per launch otherwise).  m >= Mloc: a padding
+// block of the grid (block-uniform), which leaves at once.
+struct AcycBlock {
+  int unit, m;
+};
+__device__ __forceinline__ AcycBlock acyc_xcd_block() {
+  const int L = blockIdx.x + gridDim.x * blockIdx.y, tq = L >> 3;
+  return {tq % (int)gridDim.x, (tq / (int)gridDim.x) * 8 + (L & 7)};
+}
+
 // FOUR: d > 48 (all four row / column tiles in use); the d <= 48 instantiation skips the fourth wave's products and the fourth column tile
 template <bool FOUR>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_acyc_bf(const float* __restrict__ scores, float* __restrict__ part, Key2 carry, int m0,
-                                                 int M_global, int Mloc, int d, int Sa, int cpb, float alpha, float tau, int layout,
-                                                 int tiny, int n_acyc_blk) {
+                                                 int M_global, int Mloc, int d, int Sa, float alpha, float tau, int layout, int tiny) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   unsigned char* const sb = reinterpret_cast<unsigned char*>(smem);
-  // XCD-aware block order (grid = (blocks per particle, particles rounded up to 8)): workgroups go round-robin to the 8 XCDs in the
-  // order of their linear id L; L = 8 (gridDim.x p_hi + u) + p_lo puts all blocks u of particle 8 p_hi + p_lo on XCD p_lo, so a
-  // particle's score matrix is fetched into one L2 instead of all eight (17 MB of L2 misses per launch otherwise).
-  const int L = blockIdx.x + gridDim.x * blockIdx.y, p_lo = L & 7, tq = L >> 3;
-  const int bx = tq % (int)gridDim.x, m = (tq / (int)gridDim.x) * 8 + p_lo;
-  if (m >= Mloc) return;  // (block-uniform)
-  const int blk = bx, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const auto [unit, m] = acyc_xcd_block();
+  if (m >= Mloc) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g4 = lane >> 4, r = lane & 15;
   const int a = 16 * wave + r, b0 = 4 * g4;  // row; first column within a tile
   const Key2 km = rng_split_row_uniform(carry, (uint32_t)M_global + 1u, (uint32_t)(m0 + m) + 1u, layout);  // dibs.py:595: key used directly
@@ -199,108 +206,107 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   const bool row_active = FOUR || 16 * wave < d;
   const int wr_off = a * 32 + ((g4 + (r >> 2)) & 3) * 8;
   const int rd_off = (4 * g4 + (r >> 2)) * 32 + (((r & 3) + g4) & 3) * 8;
-  float* const po = part + ((size_t)m * n_acyc_blk + blk) * dd + (size_t)a * d;
+  float* const po = part + ((size_t)m * n_units + unit) * dd + (size_t)a * d;
   f32x4 g[ABF_NT], gnext[ABF_NT];
 #pragma unroll
   for (int tj = 0; tj < ABF_NT; ++tj) gnext[tj] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // (the sum over the block's chains stays in registers: a read-modify-write of `part` per chain instead cost 10 us per launch)
+  // (the sum over the pair's two chains stays in registers: a read-modify-write of `part` per chain instead cost 10 us per launch)
   f32x4 out[ABF_NT];
 #pragma unroll
   for (int tj = 0; tj < ABF_NT; ++tj) out[tj] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  for (int c = 0; c < cpb; ++c) {
-    const int unit = blk * cpb + c;
-    if (unit >= n_units) break;
-    for (int hf = 0; hf < 2; ++hf) {
-      const int sa = unit + hf * (Sa >> 1);
-      const float* sml = sm;
-      asm volatile("" : "+s"(sml));  // opaque per pass: keeps exp(-alpha s) out of loop-invariant registers
-      // soft graph of this chain (hf = 0 draws both chains of the pair)
+  // (the d > 48 instantiation takes its two chains as straight-line code: as a loop it spills 44 bytes, unrolled none; the d <= 48 one
+  //  the other way round, 0 as a loop and 16 unrolled -- both sit at the 168 registers of three waves per SIMD)
+#pragma unroll FOUR ? 2 : 1
+  for (int hf = 0; hf < 2; ++hf) {
+    const int sa = unit + hf * (Sa >> 1);
+    const float* sml = sm;
+    asm volatile("" : "+s"(sml));  // opaque per pass: keeps exp(-alpha s) out of loop-invariant registers
+    // soft graph of this chain (hf = 0 draws both chains of the pair)
 #pragma unroll
-      for (int tj = 0; tj < ABF_NT; ++tj)
+    for (int tj = 0; tj < ABF_NT; ++tj)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int b = b0 + 16 * tj + i;
-          float gv = 0.f;
-          if (a < d && b < d && a != b) {
-            if (hf == 1) {
-              gv = gnext[tj][i];
+      for (int i = 0; i < 4; ++i) {
+        const int b = b0 + 16 * tj + i;
+        float gv = 0.f;
+        if (a < d && b < d && a != b) {
+          if (hf == 1) {
+            gv = gnext[tj][i];
+          } else {
+            const float as = alpha * sml[a * d + b];
+            const float ea = fast ? expf(-as) : as;
+            uint32_t y0, y1;
+            // counter sa d d + a d + b, b = b0 + 16 tj + i: the lane's part is a d + b0
+            threefry2x32_uh(tk, (uint32_t)(a * d + b0), (uint32_t)((uint64_t)sa * dd) + (uint32_t)(16 * tj + i), (uint32_t)(nbits >> 1), y0, y1);
+            if (fast) {
+              const float u0 = rng_uniform(y0, ulo, 1.0f), u1 = rng_uniform(y1, ulo, 1.0f);
+              // (saturated edges -- exp(-alpha s) below the rounding of the denominator, every step once alpha s > ~17 -- must give exactly
+              //  1 as the reference's sigmoid does: g (1 - g) = 0 multiplies matrix-power entries of any size; u * rcp(u) is 1 +- 1 ulp)
+              const float den0 = fmaf(1.0f - u0, ea, u0), den1 = fmaf(1.0f - u1, ea, u1);
+              gv = den0 == u0 ? 1.0f : u0 * __builtin_amdgcn_rcpf(den0);
+              gnext[tj][i] = den1 == u1 ? 1.0f : u1 * __builtin_amdgcn_rcpf(den1);
             } else {
-              const float as = alpha * sml[a * d + b];
-              const float ea = fast ? expf(-as) : as;
-              uint32_t y0, y1;
-              // counter sa d d + a d + b, b = b0 + 16 tj + i: the lane's part is a d + b0
-              threefry2x32_uh(tk, (uint32_t)(a * d + b0), (uint32_t)((uint64_t)sa * dd) + (uint32_t)(16 * tj + i), (uint32_t)(nbits >> 1), y0, y1);
-              if (fast) {
-                const float u0 = rng_uniform(y0, ulo, 1.0f), u1 = rng_uniform(y1, ulo, 1.0f);
-                // (saturated edges -- exp(-alpha s) below the rounding of the denominator, every step once alpha s > ~17 -- must give exactly
-                //  1 as the reference's sigmoid does: g (1 - g) = 0 multiplies matrix-power entries of any size; u * rcp(u) is 1 +- 1 ulp)
-                const float den0 = fmaf(1.0f - u0, ea, u0), den1 = fmaf(1.0f - u1, ea, u1);
-                gv = den0 == u0 ? 1.0f : u0 * __builtin_amdgcn_rcpf(den0);
-                gnext[tj][i] = den1 == u1 ? 1.0f : u1 * __builtin_amdgcn_rcpf(den1);
-              } else {
-                gv = 1.0f / (1.0f + expf(-tau * (rng_logistic(y0, tiny) + ea)));
-                gnext[tj][i] = 1.0f / (1.0f + expf(-tau * (rng_logistic(y1, tiny) + ea)));
-              }
+              gv = 1.0f / (1.0f + expf(-tau * (rng_logistic(y0, tiny) + ea)));
+              gnext[tj][i] = 1.0f / (1.0f + expf(-tau * (rng_logistic(y1, tiny) + ea)));
             }
           }
-          g[tj][i] = gv;
         }
-      AbfFrag A;
-      f32x4 acc[ABF_NT];
-      abf_m0(g, acc, a, b0, d, inv_d);
-      abf_make_frag(acc, A);
-      int cur = 0;  // image holding the running power
-      abf_store_image(sb, wr_off, A);
-      if (!FOUR && !row_active) abf_store_image(sb + ABF_IMG_BYTES, wr_off, A);  // (all zero; the previous chain's float copy may have covered these rows)
-      __syncthreads();
-      // left-to-right binary powering of e = d - 1 (>= 32 here)
-      const int ex = d - 1;
-      const int hb = 31 - __builtin_clz((unsigned)ex);
-      for (int bit = hb - 1; bit >= 0; --bit) {
-        const bool mult = (ex >> bit) & 1, last_sq = bit == 0 && !mult;
-        if (row_active) abf_matmul<FOUR>(acc, A, sb + cur, rd_off);  // P <- P P
-        cur ^= ABF_IMG_BYTES;
-        if (!last_sq) {
-          if (row_active) {
-            abf_make_frag(acc, A);
-            abf_store_image(sb + cur, wr_off, A);
-          }
-          __syncthreads();
-          if (mult) {  // P <- M P
-            f32x4 mv[ABF_NT];
-            AbfFrag A0;
-            abf_m0(g, mv, a, b0, d, inv_d);
-            abf_make_frag(mv, A0);
-            if (row_active) abf_matmul<FOUR>(acc, A0, sb + cur, rd_off);
-            cur ^= ABF_IMG_BYTES;
-            if (bit != 0) {
-              if (row_active) {
-                abf_make_frag(acc, A);
-                abf_store_image(sb + cur, wr_off, A);
-              }
-              __syncthreads();
+        g[tj][i] = gv;
+      }
+    AbfFrag A;
+    f32x4 acc[ABF_NT];
+    abf_m0(g, acc, a, b0, d, inv_d);
+    abf_make_frag(acc, A);
+    int cur = 0;  // image holding the running power
+    abf_store_image(sb, wr_off, A);
+    if (!FOUR && !row_active) abf_store_image(sb + ABF_IMG_BYTES, wr_off, A);  // (all zero; the previous chain's float copy may have covered these rows)
+    __syncthreads();
+    // left-to-right binary powering of e = d - 1 (>= 32 here)
+    const int ex = d - 1;
+    const int hb = 31 - __builtin_clz((unsigned)ex);
+    for (int bit = hb - 1; bit >= 0; --bit) {
+      const bool mult = (ex >> bit) & 1, last_sq = bit == 0 && !mult;
+      if (row_active) abf_matmul<FOUR>(acc, A, sb + cur, rd_off);  // P <- P P
+      cur ^= ABF_IMG_BYTES;
+      if (!last_sq) {
+        if (row_active) {
+          abf_make_frag(acc, A);
+          abf_store_image(sb + cur, wr_off, A);
+        }
+        __syncthreads();
+        if (mult) {  // P <- M P
+          f32x4 mv[ABF_NT];
+          AbfFrag A0;
+          abf_m0(g, mv, a, b0, d, inv_d);
+          abf_make_frag(mv, A0);
+          if (row_active) abf_matmul<FOUR>(acc, A0, sb + cur, rd_off);
+          cur ^= ABF_IMG_BYTES;
+          if (bit != 0) {
+            if (row_active) {
+              abf_make_frag(acc, A);
+              abf_store_image(sb + cur, wr_off, A);
             }
+            __syncthreads();
           }
         }
       }
-      // acc = rows of M^{d-1}; through the free image as float [row][ABF_LDT] to read it transposed
-      float* T = reinterpret_cast<float*>(sb + cur);
-#pragma unroll
-      for (int tj = 0; tj < ABF_NT; ++tj) *reinterpret_cast<f32x4*>(T + a * ABF_LDT + 16 * tj + b0) = acc[tj];
-      __syncthreads();
-      const float ta = tau * alpha;
-#pragma unroll
-      for (int tj = 0; tj < ABF_NT; ++tj)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int b = b0 + 16 * tj + i;
-          const float gv = g[tj][i];  // 0 outside the matrix and on the diagonal
-          const float v = T[b * ABF_LDT + a] * (ta * gv * (1.0f - gv));
-          out[tj][i] += v;
-        }
-      __syncthreads();  // T is the image the next chain's first product writes
     }
+    // acc = rows of M^{d-1}; through the free image as float [row][ABF_LDT] to read it transposed
+    float* T = reinterpret_cast<float*>(sb + cur);
+#pragma unroll
+    for (int tj = 0; tj < ABF_NT; ++tj) *reinterpret_cast<f32x4*>(T + a * ABF_LDT + 16 * tj + b0) = acc[tj];
+    __syncthreads();
+    const float ta = tau * alpha;
+#pragma unroll
+    for (int tj = 0; tj < ABF_NT; ++tj)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int b = b0 + 16 * tj + i;
+        const float gv = g[tj][i];  // 0 outside the matrix and on the diagonal
+        const float v = T[b * ABF_LDT + a] * (ta * gv * (1.0f - gv));
+        out[tj][i] += v;
+      }
+    __syncthreads();  // T is the image the next chain's first product writes
   }
   if (a < d) {
 #pragma unroll
@@ -320,7 +326,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 //       last k-step's second half has no rows in the image: those fragment reads go to a zeroed 512-byte page (the left operand's pieces
 //       are zero there anyway, but stale LDS bits could be NaN patterns).  Replaces the f32-MFMA k_acyc<NT> at these sizes (BASELINE
 //       config 5 is d = 100): six 16-cycle bf16 MFMAs per 16 x 16 x 32 block instead of eight 32-cycle f32 ones.
-// grid = (ceil(Sa / 2 / cpb), Mloc rounded up to 8; re-indexed XCD-aware inside), block = 64 NT, dynamic LDS = abfw_lds_bytes(NT)
+// grid = (Sa / 2, Mloc rounded up to 8; re-indexed XCD-aware inside: acyc_xcd_block), block = 64 NT, dynamic LDS = abfw_lds_bytes(NT)
 // ------------------------------------------------------------------------------------------------
 template <int NT>
 struct Abfw {
@@ -438,15 +444,14 @@ __device__ __forceinline__ void abfw_m0(const f32x4 (&g)[NT], f32x4 (&v)[NT], in
 
 template <int NT>
 __global__ __launch_bounds__(64 * NT) void k_acyc_bfw(const float* __restrict__ scores, float* __restrict__ part, Key2 carry, int m0, int M_global,
-                                                      int Mloc, int d, int Sa, int cpb, float alpha, float tau, int layout, int tiny, int n_acyc_blk) {
+                                                      int Mloc, int d, int Sa, float alpha, float tau, int layout, int tiny) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   unsigned char* const sb = reinterpret_cast<unsigned char*>(smem);
   constexpr int IMG = Abfw<NT>::IMG_BYTES, LDT = Abfw<NT>::LDT;
   unsigned char* const zero = sb + 2 * IMG;  // 512 zero bytes
-  const int L = blockIdx.x + gridDim.x * blockIdx.y, p_lo = L & 7, tq = L >> 3;
-  const int bx = tq % (int)gridDim.x, m = (tq / (int)gridDim.x) * 8 + p_lo;
-  if (m >= Mloc) return;  // (block-uniform)
-  const int blk = bx, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const auto [unit, m] = acyc_xcd_block();
+  if (m >= Mloc) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g4 = lane >> 4, r = lane & 15;
   const int a = 16 * wave + r, b0 = 4 * g4;
   const Key2 km = rng_split_row_uniform(carry, (uint32_t)M_global + 1u, (uint32_t)(m0 + m) + 1u, layout);  // dibs.py:595: key used directly
@@ -459,7 +464,7 @@ __global__ __launch_bounds__(64 * NT) void k_acyc_bfw(const float* __restrict__ 
   const TfKeys tk = tf_keys(km);
   const int wr_off = a * 32 + ((g4 + (r >> 2)) & 3) * 8;
   const int rd_off = (4 * g4 + (r >> 2)) * 32 + (((r & 3) + g4) & 3) * 8;
-  float* const po = part + ((size_t)m * n_acyc_blk + blk) * dd + (size_t)a * d;
+  float* const po = part + ((size_t)m * n_units + unit) * dd + (size_t)a * d;
   if (tid < 128) reinterpret_cast<uint32_t*>(zero)[tid] = 0u;
   f32x4 g[NT], gnext[NT], out[NT];
 #pragma unroll
@@ -467,88 +472,86 @@ __global__ __launch_bounds__(64 * NT) void k_acyc_bfw(const float* __restrict__ 
     gnext[tj] = f32x4{0.f, 0.f, 0.f, 0.f};
     out[tj] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
-  for (int c = 0; c < cpb; ++c) {
-    const int unit = blk * cpb + c;
-    if (unit >= n_units) break;
-    for (int hf = 0; hf < 2; ++hf) {
-      const int sa = unit + hf * (Sa >> 1);
-      const float* sml = sm;
-      asm volatile("" : "+s"(sml));  // opaque per pass: keeps exp(-alpha s) out of loop-invariant registers
+  // (NT = 7 at 256 registers: 148 bytes of scratch unrolled, 192 as a loop; NT = 5 spills 12 bytes unrolled and none as a loop)
+#pragma unroll NT == 7 ? 2 : 1
+  for (int hf = 0; hf < 2; ++hf) {
+    const int sa = unit + hf * (Sa >> 1);
+    const float* sml = sm;
+    asm volatile("" : "+s"(sml));  // opaque per pass: keeps exp(-alpha s) out of loop-invariant registers
 #pragma unroll
-      for (int tj = 0; tj < NT; ++tj)
+    for (int tj = 0; tj < NT; ++tj)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int b = b0 + 16 * tj + i;
-          float gv = 0.f;
-          if (a < d && b < d && a != b) {
-            if (hf == 1) {
-              gv = gnext[tj][i];
+      for (int i = 0; i < 4; ++i) {
+        const int b = b0 + 16 * tj + i;
+        float gv = 0.f;
+        if (a < d && b < d && a != b) {
+          if (hf == 1) {
+            gv = gnext[tj][i];
+          } else {
+            const float as = alpha * sml[a * d + b];
+            const float ea = fast ? expf(-as) : as;
+            uint32_t y0, y1;
+            // counter sa d d + a d + b, b = b0 + 16 tj + i: the lane's part is a d + b0
+            threefry2x32_uh(tk, (uint32_t)(a * d + b0), (uint32_t)((uint64_t)sa * dd) + (uint32_t)(16 * tj + i), (uint32_t)(nbits >> 1), y0, y1);
+            if (fast) {
+              const float u0 = rng_uniform(y0, ulo, 1.0f), u1 = rng_uniform(y1, ulo, 1.0f);
+              const float den0 = fmaf(1.0f - u0, ea, u0), den1 = fmaf(1.0f - u1, ea, u1);
+              gv = den0 == u0 ? 1.0f : u0 * __builtin_amdgcn_rcpf(den0);   // (saturated edges give exactly 1: see k_acyc_bf)
+              gnext[tj][i] = den1 == u1 ? 1.0f : u1 * __builtin_amdgcn_rcpf(den1);
             } else {
-              const float as = alpha * sml[a * d + b];
-              const float ea = fast ? expf(-as) : as;
-              uint32_t y0, y1;
-              // counter sa d d + a d + b, b = b0 + 16 tj + i: the lane's part is a d + b0
-              threefry2x32_uh(tk, (uint32_t)(a * d + b0), (uint32_t)((uint64_t)sa * dd) + (uint32_t)(16 * tj + i), (uint32_t)(nbits >> 1), y0, y1);
-              if (fast) {
-                const float u0 = rng_uniform(y0, ulo, 1.0f), u1 = rng_uniform(y1, ulo, 1.0f);
-                const float den0 = fmaf(1.0f - u0, ea, u0), den1 = fmaf(1.0f - u1, ea, u1);
-                gv = den0 == u0 ? 1.0f : u0 * __builtin_amdgcn_rcpf(den0);   // (saturated edges give exactly 1: see k_acyc_bf)
-                gnext[tj][i] = den1 == u1 ? 1.0f : u1 * __builtin_amdgcn_rcpf(den1);
-              } else {
-                gv = 1.0f / (1.0f + expf(-tau * (rng_logistic(y0, tiny) + ea)));
-                gnext[tj][i] = 1.0f / (1.0f + expf(-tau * (rng_logistic(y1, tiny) + ea)));
-              }
+              gv = 1.0f / (1.0f + expf(-tau * (rng_logistic(y0, tiny) + ea)));
+              gnext[tj][i] = 1.0f / (1.0f + expf(-tau * (rng_logistic(y1, tiny) + ea)));
             }
           }
-          g[tj][i] = gv;
         }
-      AbfwFrag<NT> A;
-      f32x4 acc[NT];
-      abfw_m0<NT>(g, acc, a, b0, d, inv_d);
-      abfw_make_frag<NT>(acc, A);
-      int cur = 0;
-      abfw_store_image<NT>(sb, wr_off, A);
-      __syncthreads();
-      const int ex = d - 1;
-      const int hb = 31 - __builtin_clz((unsigned)ex);
-      for (int bit = hb - 1; bit >= 0; --bit) {
-        const bool mult = (ex >> bit) & 1, last_sq = bit == 0 && !mult;
-        abfw_matmul<NT>(acc, A, sb + cur, rd_off, zero);  // P <- P P
-        cur ^= IMG;
-        if (!last_sq) {
-          abfw_make_frag<NT>(acc, A);
-          abfw_store_image<NT>(sb + cur, wr_off, A);
-          __syncthreads();
-          if (mult) {  // P <- M P
-            f32x4 mv[NT];
-            AbfwFrag<NT> A0;
-            abfw_m0<NT>(g, mv, a, b0, d, inv_d);
-            abfw_make_frag<NT>(mv, A0);
-            abfw_matmul<NT>(acc, A0, sb + cur, rd_off, zero);
-            cur ^= IMG;
-            if (bit != 0) {
-              abfw_make_frag<NT>(acc, A);
-              abfw_store_image<NT>(sb + cur, wr_off, A);
-              __syncthreads();
-            }
+        g[tj][i] = gv;
+      }
+    AbfwFrag<NT> A;
+    f32x4 acc[NT];
+    abfw_m0<NT>(g, acc, a, b0, d, inv_d);
+    abfw_make_frag<NT>(acc, A);
+    int cur = 0;
+    abfw_store_image<NT>(sb, wr_off, A);
+    __syncthreads();
+    const int ex = d - 1;
+    const int hb = 31 - __builtin_clz((unsigned)ex);
+    for (int bit = hb - 1; bit >= 0; --bit) {
+      const bool mult = (ex >> bit) & 1, last_sq = bit == 0 && !mult;
+      abfw_matmul<NT>(acc, A, sb + cur, rd_off, zero);  // P <- P P
+      cur ^= IMG;
+      if (!last_sq) {
+        abfw_make_frag<NT>(acc, A);
+        abfw_store_image<NT>(sb + cur, wr_off, A);
+        __syncthreads();
+        if (mult) {  // P <- M P
+          f32x4 mv[NT];
+          AbfwFrag<NT> A0;
+          abfw_m0<NT>(g, mv, a, b0, d, inv_d);
+          abfw_make_frag<NT>(mv, A0);
+          abfw_matmul<NT>(acc, A0, sb + cur, rd_off, zero);
+          cur ^= IMG;
+          if (bit != 0) {
+            abfw_make_frag<NT>(acc, A);
+            abfw_store_image<NT>(sb + cur, wr_off, A);
+            __syncthreads();
           }
         }
       }
-      float* T = reinterpret_cast<float*>(sb + cur);
-#pragma unroll
-      for (int tj = 0; tj < NT; ++tj) *reinterpret_cast<f32x4*>(T + a * LDT + 16 * tj + b0) = acc[tj];
-      __syncthreads();
-      const float ta = tau * alpha;
-#pragma unroll
-      for (int tj = 0; tj < NT; ++tj)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int b = b0 + 16 * tj + i;
-          const float gv = g[tj][i];
-          out[tj][i] += T[b * LDT + a] * (ta * gv * (1.0f - gv));
-        }
-      __syncthreads();
     }
+    float* T = reinterpret_cast<float*>(sb + cur);
+#pragma unroll
+    for (int tj = 0; tj < NT; ++tj) *reinterpret_cast<f32x4*>(T + a * LDT + 16 * tj + b0) = acc[tj];
+    __syncthreads();
+    const float ta = tau * alpha;
+#pragma unroll
+    for (int tj = 0; tj < NT; ++tj)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int b = b0 + 16 * tj + i;
+        const float gv = g[tj][i];
+        out[tj][i] += T[b * LDT + a] * (ta * gv * (1.0f - gv));
+      }
+    __syncthreads();
   }
   if (a < d) {
 #pragma unroll

@@ -32,7 +32,7 @@
 // Measured and dropped: skipping the seven products of a chain whose soft graph is saturated everywhere (g (1 - g) = 0 on all edges, the
 // contribution is exactly zero) -- a flag per chain from the draw loop costs 2-3 us per launch and never fires: at t = 100 ... 1 000 of the
 // headline trajectory every chain keeps live edges (74.9 us per launch throughout, scripts/gpu_steady_bench.py).
-// grid = (ceil(Sa / 2 / cpb), Mloc rounded up to 8; re-indexed XCD-aware inside), block = 256, dynamic LDS = AHF_LDS_BYTES
+// grid = (Sa / 2, Mloc rounded up to 8; re-indexed XCD-aware inside: acyc_xcd_block), block = 256, dynamic LDS = AHF_LDS_BYTES
 // ------------------------------------------------------------------------------------------------
 typedef _Float16 ahf_f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 ahf_f16x2 __attribute__((ext_vector_type(2)));
@@ -251,17 +251,14 @@ __device__ __forceinline__ void ahf_m0(const f32x4 (&g)[AHF_NT], f32x4 (&v)[AHF_
 // FOUR: d > 48 (all four row / column tiles in use); the d <= 48 instantiation skips the fourth wave's products and the fourth column tile
 template <bool FOUR, int WPE>
 __device__ __forceinline__ void acyc_hf_block(const float* __restrict__ scores, const float* __restrict__ eas, float* __restrict__ part, Key2 carry, int m0,
-                                              int M_global, int Mloc, int d, int Sa, int cpb, float alpha, float tau, int layout,
-                                              int tiny, int n_acyc_blk) {
+                                              int M_global, int Mloc, int d, int Sa, float alpha, float tau, int layout, int tiny) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   unsigned char* const sb = reinterpret_cast<unsigned char*>(smem);
   uint32_t* const slots = reinterpret_cast<uint32_t*>(sb + 2 * AHF_IMG_STRIDE);  // [2][4] row maxima of the waves, ping-pong
   float* const zpage = reinterpret_cast<float*>(sb + 2 * AHF_IMG_STRIDE + 64);     // [64] zeros: what the lanes of rows >= d read as their graph
-  // XCD-aware block order: all blocks of a particle on one XCD (see k_acyc_bf)
-  const int L = blockIdx.x + gridDim.x * blockIdx.y, p_lo = L & 7, tq = L >> 3;
-  const int bx = tq % (int)gridDim.x, m = (tq / (int)gridDim.x) * 8 + p_lo;
-  if (m >= Mloc) return;  // (block-uniform)
-  const int blk = bx, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const auto [unit, m] = acyc_xcd_block();
+  if (m >= Mloc) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g4 = lane >> 4, r = lane & 15;
   const int a = 16 * wave + r, b0 = 4 * g4;  // row; first column within a tile
   const Key2 km = rng_split_row_uniform(carry, (uint32_t)M_global + 1u, (uint32_t)(m0 + m) + 1u, layout);  // dibs.py:595: key used directly
@@ -281,7 +278,7 @@ __device__ __forceinline__ void acyc_hf_block(const float* __restrict__ scores, 
   const bool row_active = FOUR || 16 * wave < d;
   const int wr_off = a * 32 + ((g4 + (r >> 2)) & 3) * 8;
   const int rd_off = (4 * g4 + (r >> 2)) * 32 + (((r & 3) + g4) & 3) * 8;
-  float* const po = part + ((size_t)m * n_acyc_blk + blk) * dd + (size_t)a * d;
+  float* const po = part + ((size_t)m * n_units + unit) * dd + (size_t)a * d;
   f32x4 g[AHF_NT], gnext[AHF_NT], out[AHF_NT];
 #pragma unroll
   for (int tj = 0; tj < AHF_NT; ++tj) {
@@ -291,140 +288,167 @@ __device__ __forceinline__ void acyc_hf_block(const float* __restrict__ scores, 
   const float s0 = ahf_pow2(AHF_E0);
   int par = 0;  // slot set the next product publishes its maxima in
 
-  for (int c = 0; c < cpb; ++c) {
-    const int unit = blk * cpb + c;
-    if (unit >= n_units) break;
-    // Soft graphs of BOTH chains of the pair, drawn in ELEMENT order -- thread tid takes elements e = tid, tid + 256, ... of the d x d
-    // matrix: every lane busy (10 wave-draws per wave at d = 50 where the owner-lane order needs 14, the fourth wave's and the fourth
-    // column tile's mostly for idle lanes), the Threefry counter is base + e, the score loads are coalesced and requested together --
-    // and handed to the owning lanes through LDS: G0 / G1 [d d] float, LINEAR in e, over the (free) images.  The loop carries nothing
-    // per element but the draw itself: the index is tid + 256 k with k wave-uniform, so the score address advances on the scalar
-    // unit and the LDS address by a constant; the diagonal is drawn like any other element and cleared by its owner lane below
-    // (M ignores it, the back-projection needs g = 0 there); the last, partial iteration is peeled, the full ones test no bounds.
-    {
-      const int sa = unit;
-      float* const G0 = reinterpret_cast<float*>(sb);
-      float* const G1 = reinterpret_cast<float*>(sb + AHF_IMG_STRIDE);
-      const int ndd = (int)dd;
-      const uint32_t cbase = (uint32_t)((uint64_t)sa * dd), chalf = (uint32_t)(nbits >> 1);
-      if (fast) {
-        const int nfull = ndd >> 8, rem = ndd & 255;  // (d >= 33: nfull >= 4)
-        const bool in_rem = tid < rem;
-        // scores through a buffer descriptor: lane offset 4 tid, the iteration's offset in an SGPR (no per-lane 64-bit address)
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sm), 0, 4 * ndd, 0x00020000);
-        const uint32_t voff = 4u * (uint32_t)tid;
-        uint32_t soff = 0u, off = cbase;
-        float* gp = G0 + tid;
-        const auto draw = [&](float ea) {
-          uint32_t y0, y1;
-          threefry2x32_uh(tk, (uint32_t)tid, off, chalf, y0, y1);  // counter cbase + e: only tid is the lane's
-          const abf_f32x2 u = ahf_uniform2(y0, y1, ulo);
-          // (saturated edges must give exactly 1 as the reference's sigmoid does: see k_acyc_bf)
-          const abf_f32x2 den = __builtin_elementwise_fma(1.0f - u, abf_f32x2{ea, ea}, u);
-          const abf_f32x2 q = u * abf_f32x2{__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
-          gp[0] = den.x == u.x ? 1.0f : q.x;
-          gp[AHF_IMG_STRIDE / 4] = den.y == u.y ? 1.0f : q.y;
-        };
-        float s_next = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, soff, 0));  // (requested one draw ahead)
-        for (int k = 0; k < nfull - 1; ++k) {
-          const float s_cur = s_next;
-          soff += 1024u;
-          s_next = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, soff, 0));
-          draw(s_cur);
-          off += 256u;
-          gp += 256;
-        }
+  // Soft graphs of BOTH chains of the pair, drawn in ELEMENT order -- thread tid takes elements e = tid, tid + 256, ... of the d x d
+  // matrix: every lane busy (10 wave-draws per wave at d = 50 where the owner-lane order needs 14, the fourth wave's and the fourth
+  // column tile's mostly for idle lanes), the Threefry counter is base + e, the score loads are coalesced and requested together --
+  // and handed to the owning lanes through LDS: G0 / G1 [d d] float, LINEAR in e, over the (free) images.  The loop carries nothing
+  // per element but the draw itself: the index is tid + 256 k with k wave-uniform, so the score address advances on the scalar
+  // unit and the LDS address by a constant; the diagonal is drawn like any other element and cleared by its owner lane below
+  // (M ignores it, the back-projection needs g = 0 there); the last, partial iteration is peeled, the full ones test no bounds.
+  {
+    const int sa = unit;
+    float* const G0 = reinterpret_cast<float*>(sb);
+    float* const G1 = reinterpret_cast<float*>(sb + AHF_IMG_STRIDE);
+    const int ndd = (int)dd;
+    const uint32_t cbase = (uint32_t)((uint64_t)sa * dd), chalf = (uint32_t)(nbits >> 1);
+    if (fast) {
+      const int nfull = ndd >> 8, rem = ndd & 255;  // (d >= 33: nfull >= 4)
+      const bool in_rem = tid < rem;
+      // scores through a buffer descriptor: lane offset 4 tid, the iteration's offset in an SGPR (no per-lane 64-bit address)
+      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sm), 0, 4 * ndd, 0x00020000);
+      const uint32_t voff = 4u * (uint32_t)tid;
+      uint32_t soff = 0u, off = cbase;
+      float* gp = G0 + tid;
+      const auto draw = [&](float ea) {
+        uint32_t y0, y1;
+        threefry2x32_uh(tk, (uint32_t)tid, off, chalf, y0, y1);  // counter cbase + e: only tid is the lane's
+        const abf_f32x2 u = ahf_uniform2(y0, y1, ulo);
+        // (saturated edges must give exactly 1 as the reference's sigmoid does: see k_acyc_bf)
+        const abf_f32x2 den = __builtin_elementwise_fma(1.0f - u, abf_f32x2{ea, ea}, u);
+        const abf_f32x2 q = u * abf_f32x2{__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
+        gp[0] = den.x == u.x ? 1.0f : q.x;
+        gp[AHF_IMG_STRIDE / 4] = den.y == u.y ? 1.0f : q.y;
+      };
+      float s_next = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, soff, 0));  // (requested one draw ahead)
+      for (int k = 0; k < nfull - 1; ++k) {
         const float s_cur = s_next;
-        if (in_rem) s_next = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, soff + 1024u, 0));
-        draw(s_cur);  // the last full iteration
-        if (in_rem) {
-          off += 256u;
-          gp += 256;
-          draw(s_next);
-        }
-      } else {
-        for (int k = 0; 256 * k < ndd; ++k) {
-          const int e = tid + 256 * k;
-          if (e < ndd) {
-            const float ea = alpha * sm[e];
-            uint32_t y0, y1;
-            threefry2x32_uh(tk, (uint32_t)tid, cbase + 256u * (uint32_t)k, chalf, y0, y1);
-            G0[e] = 1.0f / (1.0f + expf(-tau * (rng_logistic(y0, tiny) + ea)));
-            G1[e] = 1.0f / (1.0f + expf(-tau * (rng_logistic(y1, tiny) + ea)));
-          }
+        soff += 1024u;
+        s_next = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, soff, 0));
+        draw(s_cur);
+        off += 256u;
+        gp += 256;
+      }
+      const float s_cur = s_next;
+      if (in_rem) s_next = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, soff + 1024u, 0));
+      draw(s_cur);  // the last full iteration
+      if (in_rem) {
+        off += 256u;
+        gp += 256;
+        draw(s_next);
+      }
+    } else {
+      for (int k = 0; 256 * k < ndd; ++k) {
+        const int e = tid + 256 * k;
+        if (e < ndd) {
+          const float ea = alpha * sm[e];
+          uint32_t y0, y1;
+          threefry2x32_uh(tk, (uint32_t)tid, cbase + 256u * (uint32_t)k, chalf, y0, y1);
+          G0[e] = 1.0f / (1.0f + expf(-tau * (rng_logistic(y0, tiny) + ea)));
+          G1[e] = 1.0f / (1.0f + expf(-tau * (rng_logistic(y1, tiny) + ea)));
         }
       }
-      __syncthreads();
-      // owner lanes: row a, columns 16 tj + b0 .. + 3.  Rows are 4-byte aligned only (odd d): dword reads.  Lanes of rows beyond the
-      // matrix read the zero page.  Only the tile that holds column d - 1 (a constant of the instantiation) has columns to mask:
-      // they hold the next row's elements.
-      {
-        const float* const r0 = a < d ? G0 + a * d + b0 : zpage;
-        const float* const r1 = a < d ? G1 + a * d + b0 : zpage;
-        constexpr int TL = FOUR ? 3 : 2;
-#pragma unroll
-        for (int tj = 0; tj < AHF_NT; ++tj) {
-          f32x4 v0 = f32x4{0.f, 0.f, 0.f, 0.f}, v1 = v0;
-          if (tj <= TL) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              v0[i] = r0[16 * tj + i];
-              v1[i] = r1[16 * tj + i];
-            }
-            if (tj == TL) {
-#pragma unroll
-              for (int i = 0; i < 4; ++i) {
-                const bool in = b0 + 16 * TL + i < d;
-                v0[i] = in ? v0[i] : 0.f;
-                v1[i] = in ? v1[i] : 0.f;
-              }
-            }
-          }
-          g[tj] = v0;
-          gnext[tj] = v1;
-        }
-#pragma unroll
-        for (int tj = 0; tj < AHF_NT; ++tj)
-          if (own[tj]) {
-            asm volatile("; diagonal tile");  // (see ahf_m0)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              g[tj][i] = dg[i] ? 0.f : g[tj][i];
-              gnext[tj][i] = dg[i] ? 0.f : gnext[tj][i];
-            }
-          }
-      }
-      __syncthreads();  // the images are written next
     }
-    for (int hf = 0; hf < 2; ++hf) {
-      if (hf == 1) {
+    __syncthreads();
+    // owner lanes: row a, columns 16 tj + b0 .. + 3.  Rows are 4-byte aligned only (odd d): dword reads.  Lanes of rows beyond the
+    // matrix read the zero page.  Only the tile that holds column d - 1 (a constant of the instantiation) has columns to mask:
+    // they hold the next row's elements.
+    {
+      const float* const r0 = a < d ? G0 + a * d + b0 : zpage;
+      const float* const r1 = a < d ? G1 + a * d + b0 : zpage;
+      constexpr int TL = FOUR ? 3 : 2;
 #pragma unroll
-        for (int tj = 0; tj < AHF_NT; ++tj) g[tj] = gnext[tj];
+      for (int tj = 0; tj < AHF_NT; ++tj) {
+        f32x4 v0 = f32x4{0.f, 0.f, 0.f, 0.f}, v1 = v0;
+        if (tj <= TL) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            v0[i] = r0[16 * tj + i];
+            v1[i] = r1[16 * tj + i];
+          }
+          if (tj == TL) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              const bool in = b0 + 16 * TL + i < d;
+              v0[i] = in ? v0[i] : 0.f;
+              v1[i] = in ? v1[i] : 0.f;
+            }
+          }
+        }
+        g[tj] = v0;
+        gnext[tj] = v1;
       }
-      AhfFrag A;
-      f32x4 acc[AHF_NT];
-      ahf_m0(g, acc, own, dg, inv_d);
-      ahf_make_frag(acc, s0, A);
-      AhfFrag AM;               // M's own fragments for the "times M" steps (kept when the register budget allows: WPE == 3)
-      if constexpr (WPE <= 3) AM = A;
-      int cur = 0;              // image holding the running power
-      int E = AHF_E0;           // ... as P 2^E
-      int exP = AHF_E0;         // exponent of its largest stored entry (the unit diagonal of M: exactly 2^14)
-      ahf_store_image(sb, wr_off, A);
-      if (!FOUR && !row_active) ahf_store_image(sb + AHF_IMG_STRIDE, wr_off, A);  // (all zero; the previous chain's float staging may have covered these rows)
-      __syncthreads();
-      // left-to-right binary powering of e = d - 1 (>= 32 here)
-      const int ex = d - 1;
-      const int hb = 31 - __builtin_clz((unsigned)ex);
-      int Eacc = 0;
-      for (int bit = hb - 1; bit >= 0; --bit) {
-        const bool mult = (ex >> bit) & 1, last_sq = bit == 0 && !mult;
-        if (row_active) ahf_matmul<FOUR>(acc, A, sb + cur, rd_off);  // P <- P P : acc = P^2 2^(2E) <= 64 max^2 < 2^(2 exP + 8)
-        cur ^= AHF_IMG_STRIDE;
-        Eacc = 2 * E;
-        if (!last_sq) {
-          {
-            const int sh = 7 - 2 * exP;  // stored pieces < 2^15
+#pragma unroll
+      for (int tj = 0; tj < AHF_NT; ++tj)
+        if (own[tj]) {
+          asm volatile("; diagonal tile");  // (see ahf_m0)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            g[tj][i] = dg[i] ? 0.f : g[tj][i];
+            gnext[tj][i] = dg[i] ? 0.f : gnext[tj][i];
+          }
+        }
+    }
+    __syncthreads();  // the images are written next
+  }
+  for (int hf = 0; hf < 2; ++hf) {
+    if (hf == 1) {
+#pragma unroll
+      for (int tj = 0; tj < AHF_NT; ++tj) g[tj] = gnext[tj];
+    }
+    AhfFrag A;
+    f32x4 acc[AHF_NT];
+    ahf_m0(g, acc, own, dg, inv_d);
+    ahf_make_frag(acc, s0, A);
+    AhfFrag AM;               // M's own fragments for the "times M" steps (kept when the register budget allows: WPE == 3)
+    if constexpr (WPE <= 3) AM = A;
+    int cur = 0;              // image holding the running power
+    int E = AHF_E0;           // ... as P 2^E
+    int exP = AHF_E0;         // exponent of its largest stored entry (the unit diagonal of M: exactly 2^14)
+    ahf_store_image(sb, wr_off, A);
+    if (!FOUR && !row_active) ahf_store_image(sb + AHF_IMG_STRIDE, wr_off, A);  // (all zero; the previous chain's float staging may have covered these rows)
+    __syncthreads();
+    // left-to-right binary powering of e = d - 1 (>= 32 here)
+    const int ex = d - 1;
+    const int hb = 31 - __builtin_clz((unsigned)ex);
+    int Eacc = 0;
+    for (int bit = hb - 1; bit >= 0; --bit) {
+      const bool mult = (ex >> bit) & 1, last_sq = bit == 0 && !mult;
+      if (row_active) ahf_matmul<FOUR>(acc, A, sb + cur, rd_off);  // P <- P P : acc = P^2 2^(2E) <= 64 max^2 < 2^(2 exP + 8)
+      cur ^= AHF_IMG_STRIDE;
+      Eacc = 2 * E;
+      if (!last_sq) {
+        {
+          const int sh = 7 - 2 * exP;  // stored pieces < 2^15
+          const uint32_t wm = ahf_wave_max<AHF_NT>(acc);
+          if (lane == 0) slots[par * 4 + wave] = wm;
+          if (row_active) {
+            ahf_make_frag(acc, ahf_pow2(sh), A);
+            ahf_store_image(sb + cur, wr_off, A);
+          }
+          __syncthreads();
+          const abf_u32x4 q = *reinterpret_cast<const abf_u32x4*>(slots + par * 4);
+          uint32_t mx = q.x > q.y ? q.x : q.y;
+          mx = mx > q.z ? mx : q.z;
+          mx = mx > q.w ? mx : q.w;
+          mx = __builtin_amdgcn_readfirstlane(mx);
+          E = Eacc + sh;
+          exP = (int)(mx >> 23) - 127 + sh;
+          par ^= 1;
+        }
+        if (mult) {  // P <- M P : acc = (M 2^14)(P 2^E) < 2^14 2 max < 2^(exP + 16)
+          if constexpr (WPE <= 3) {
+            if (row_active) ahf_matmul<FOUR>(acc, AM, sb + cur, rd_off);
+          } else {
+            f32x4 mv[AHF_NT];
+            AhfFrag A0;
+            ahf_m0(g, mv, own, dg, inv_d);
+            ahf_make_frag(mv, s0, A0);
+            if (row_active) ahf_matmul<FOUR>(acc, A0, sb + cur, rd_off);
+          }
+          cur ^= AHF_IMG_STRIDE;
+          Eacc = AHF_E0 + E;
+          if (bit != 0) {
+            const int sh = -1 - exP;
             const uint32_t wm = ahf_wave_max<AHF_NT>(acc);
             if (lane == 0) slots[par * 4 + wave] = wm;
             if (row_active) {
@@ -441,56 +465,25 @@ __device__ __forceinline__ void acyc_hf_block(const float* __restrict__ scores, 
             exP = (int)(mx >> 23) - 127 + sh;
             par ^= 1;
           }
-          if (mult) {  // P <- M P : acc = (M 2^14)(P 2^E) < 2^14 2 max < 2^(exP + 16)
-            if constexpr (WPE <= 3) {
-              if (row_active) ahf_matmul<FOUR>(acc, AM, sb + cur, rd_off);
-            } else {
-              f32x4 mv[AHF_NT];
-              AhfFrag A0;
-              ahf_m0(g, mv, own, dg, inv_d);
-              ahf_make_frag(mv, s0, A0);
-              if (row_active) ahf_matmul<FOUR>(acc, A0, sb + cur, rd_off);
-            }
-            cur ^= AHF_IMG_STRIDE;
-            Eacc = AHF_E0 + E;
-            if (bit != 0) {
-              const int sh = -1 - exP;
-              const uint32_t wm = ahf_wave_max<AHF_NT>(acc);
-              if (lane == 0) slots[par * 4 + wave] = wm;
-              if (row_active) {
-                ahf_make_frag(acc, ahf_pow2(sh), A);
-                ahf_store_image(sb + cur, wr_off, A);
-              }
-              __syncthreads();
-              const abf_u32x4 q = *reinterpret_cast<const abf_u32x4*>(slots + par * 4);
-              uint32_t mx = q.x > q.y ? q.x : q.y;
-              mx = mx > q.z ? mx : q.z;
-              mx = mx > q.w ? mx : q.w;
-              mx = __builtin_amdgcn_readfirstlane(mx);
-              E = Eacc + sh;
-              exP = (int)(mx >> 23) - 127 + sh;
-              par ^= 1;
-            }
-          }
         }
       }
-      // acc = rows of M^{d-1} 2^Eacc; through the free image as float [row][AHF_LDT] to read it transposed
-      float* T = reinterpret_cast<float*>(sb + cur);
-#pragma unroll
-      for (int tj = 0; tj < AHF_NT; ++tj) *reinterpret_cast<f32x4*>(T + a * AHF_LDT + 16 * tj + b0) = acc[tj];
-      __syncthreads();
-      const float ta = ldexpf(tau * alpha, -Eacc);
-#pragma unroll
-      for (int tj = 0; tj < AHF_NT; ++tj)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int b = b0 + 16 * tj + i;
-          const float gv = g[tj][i];  // 0 outside the matrix and on the diagonal
-          const float v = T[b * AHF_LDT + a] * (ta * gv * (1.0f - gv));
-          out[tj][i] += v;
-        }
-      __syncthreads();  // T is the image the next chain's first product writes
     }
+    // acc = rows of M^{d-1} 2^Eacc; through the free image as float [row][AHF_LDT] to read it transposed
+    float* T = reinterpret_cast<float*>(sb + cur);
+#pragma unroll
+    for (int tj = 0; tj < AHF_NT; ++tj) *reinterpret_cast<f32x4*>(T + a * AHF_LDT + 16 * tj + b0) = acc[tj];
+    __syncthreads();
+    const float ta = ldexpf(tau * alpha, -Eacc);
+#pragma unroll
+    for (int tj = 0; tj < AHF_NT; ++tj)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int b = b0 + 16 * tj + i;
+        const float gv = g[tj][i];  // 0 outside the matrix and on the diagonal
+        const float v = T[b * AHF_LDT + a] * (ta * gv * (1.0f - gv));
+        out[tj][i] += v;
+      }
+    __syncthreads();  // T is the image the next chain's first product writes
   }
   if (a < d) {
 #pragma unroll
@@ -504,19 +497,18 @@ __device__ __forceinline__ void acyc_hf_block(const float* __restrict__ scores, 
 }
 template <bool FOUR, int WPE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_acyc_hf(const float* __restrict__ scores, const float* __restrict__ eas, float* __restrict__ part, Key2 carry, int m0,
-                                                 int M_global, int Mloc, int d, int Sa, int cpb, float alpha, float tau, int layout,
-                                                 int tiny, int n_acyc_blk) {
-  acyc_hf_block<FOUR, WPE>(scores, eas, part, carry, m0, M_global, Mloc, d, Sa, cpb, alpha, tau, layout, tiny, n_acyc_blk);
+                                                 int M_global, int Mloc, int d, int Sa, float alpha, float tau, int layout, int tiny) {
+  acyc_hf_block<FOUR, WPE>(scores, eas, part, carry, m0, M_global, Mloc, d, Sa, alpha, tau, layout, tiny);
 }
 // batched engines (include/dibs_hip.h, per-problem hyper-parameters): alpha of the block's particle (the XCD-aware numbering of
 // acyc_hf_block) from row m / pM of the table -- block-uniform: a scalar load
 template <bool FOUR, int WPE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_acyc_hf_batch(const float* __restrict__ scores, const float* __restrict__ eas, float* __restrict__ part,
-                                                       Key2 carry, int m0, int M_global, int Mloc, int d, int Sa, int cpb,
-                                                       const ProblemHP* __restrict__ hp, int pM, float tau, int layout, int tiny, int n_acyc_blk) {
-  const int L = blockIdx.x + gridDim.x * blockIdx.y, m = ((L >> 3) / (int)gridDim.x) * 8 + (L & 7);
+                                                       Key2 carry, int m0, int M_global, int Mloc, int d, int Sa,
+                                                       const ProblemHP* __restrict__ hp, int pM, float tau, int layout, int tiny) {
+  const int m = acyc_xcd_block().m;
   if (m >= Mloc) return;  // (the padding blocks of the grid: no row of the table)
-  acyc_hf_block<FOUR, WPE>(scores, eas, part, carry, m0, M_global, Mloc, d, Sa, cpb, hp[m / pM].alpha, tau, layout, tiny, n_acyc_blk);
+  acyc_hf_block<FOUR, WPE>(scores, eas, part, carry, m0, M_global, Mloc, d, Sa, hp[m / pM].alpha, tau, layout, tiny);
 }
 
 
@@ -527,7 +519,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 //       (k_acyc_bfw needs a zero page there); the squaring bound is max (P P) <= 128 max(P)^2.  Images of 2 x NT x 32 ceil(NT/2) x 32 bytes:
 //       30 / 37 / 56 KiB each (k_acyc_bfw: 38 / 55 / 75), i.e. two blocks per CU up to NT = 6.  Replaces k_acyc_bfw (BASELINE config 5 is
 //       d = 100); DIBS_ACYC_BF16=1 keeps that one for A/B runs.
-// grid = (ceil(Sa / 2 / cpb), Mloc rounded up to 8; re-indexed XCD-aware inside), block = 64 NT, dynamic LDS = ahfw_lds_bytes(NT)
+// grid = (Sa / 2, Mloc rounded up to 8; re-indexed XCD-aware inside: acyc_xcd_block), block = 64 NT, dynamic LDS = ahfw_lds_bytes(NT)
 // ------------------------------------------------------------------------------------------------
 template <int NT>
 struct Ahfw {
@@ -611,16 +603,14 @@ struct AhfwSteps<NT, (NT + 1) / 2> {
 
 template <int NT>
 __global__ __launch_bounds__(64 * NT) void k_acyc_hfw(const float* __restrict__ scores, const float* __restrict__ eas, float* __restrict__ part, Key2 carry,
-                                                      int m0, int M_global, int Mloc, int d, int Sa, int cpb, float alpha, float tau, int layout, int tiny,
-                                                      int n_acyc_blk) {
+                                                      int m0, int M_global, int Mloc, int d, int Sa, float alpha, float tau, int layout, int tiny) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   typedef Ahfw<NT> G;
   unsigned char* const sb = reinterpret_cast<unsigned char*>(smem);
   uint32_t* const slots = reinterpret_cast<uint32_t*>(sb + 2 * G::IMG_STRIDE);  // [2][8] row maxima of the waves, ping-pong
-  const int L = blockIdx.x + gridDim.x * blockIdx.y, p_lo = L & 7, tq = L >> 3;
-  const int bx = tq % (int)gridDim.x, m = (tq / (int)gridDim.x) * 8 + p_lo;
-  if (m >= Mloc) return;  // (block-uniform)
-  const int blk = bx, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const auto [unit, m] = acyc_xcd_block();
+  if (m >= Mloc) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g4 = lane >> 4, r = lane & 15;
   const int a = 16 * wave + r, b0 = 4 * g4;
   const Key2 km = rng_split_row_uniform(carry, (uint32_t)M_global + 1u, (uint32_t)(m0 + m) + 1u, layout);  // dibs.py:595: key used directly
@@ -633,7 +623,7 @@ __global__ __launch_bounds__(64 * NT) void k_acyc_hfw(const float* __restrict__ 
   const TfKeys tk = tf_keys(km);
   const int wr_off = a * 32 + ((g4 + (r >> 2)) & 3) * 8;
   const int rd_off = (4 * g4 + (r >> 2)) * 32 + (((r & 3) + g4) & 3) * 8;
-  float* const po = part + ((size_t)m * n_acyc_blk + blk) * dd + (size_t)a * d;
+  float* const po = part + ((size_t)m * n_units + unit) * dd + (size_t)a * d;
   f32x4 g[NT], gnext[NT], out[NT];
 #pragma unroll
   for (int tj = 0; tj < NT; ++tj) {
@@ -643,100 +633,123 @@ __global__ __launch_bounds__(64 * NT) void k_acyc_hfw(const float* __restrict__ 
   const float s0 = ahf_pow2(AHF_E0);
   int par = 0;
 
-  for (int c = 0; c < cpb; ++c) {
-    const int unit = blk * cpb + c;
-    if (unit >= n_units) break;
-    // soft graphs of both chains of the pair in element order, handed to the owning lanes through LDS (see k_acyc_hf)
-    {
-      const int sa = unit;
-      float* const G0 = reinterpret_cast<float*>(sb);
-      float* const G1 = reinterpret_cast<float*>(sb + G::IMG_STRIDE);
-      const int ndd = (int)dd, ndraw = (ndd + G::NTHR - 1) / G::NTHR;
-      const int qa = G::NTHR / d, qb = G::NTHR - qa * d;
-      int ea_ = tid / d, eb_ = tid - ea_ * d;
-      float s_next = tid < ndd ? sm[tid] : 0.f;
-      const uint32_t cbase = (uint32_t)((uint64_t)sa * dd), chalf = (uint32_t)(nbits >> 1);
-      for (int k = 0; k < ndraw; ++k) {
-        const int e = tid + G::NTHR * k;
-        const float s_cur = s_next;
-        s_next = e + G::NTHR < ndd ? sm[e + G::NTHR] : 0.f;
-        if (e < ndd) {
-          float gv0 = 0.f, gv1 = 0.f;
-          if (ea_ != eb_) {
-            const float ea = fast ? s_cur : alpha * s_cur;
-            uint32_t y0, y1;
-            threefry2x32_uh(tk, (uint32_t)tid, cbase + (uint32_t)(G::NTHR * k), chalf, y0, y1);  // counter cbase + e: only tid is the lane's
-            if (fast) {
-              const float u0 = rng_uniform(y0, ulo, 1.0f), u1 = rng_uniform(y1, ulo, 1.0f);
-              const float den0 = fmaf(1.0f - u0, ea, u0), den1 = fmaf(1.0f - u1, ea, u1);
-              gv0 = den0 == u0 ? 1.0f : u0 * __builtin_amdgcn_rcpf(den0);   // (saturated edges give exactly 1: see k_acyc_bf)
-              gv1 = den1 == u1 ? 1.0f : u1 * __builtin_amdgcn_rcpf(den1);
-            } else {
-              gv0 = 1.0f / (1.0f + expf(-tau * (rng_logistic(y0, tiny) + ea)));
-              gv1 = 1.0f / (1.0f + expf(-tau * (rng_logistic(y1, tiny) + ea)));
-            }
-          }
-          G0[ea_ * G::LDT + eb_] = gv0;
-          G1[ea_ * G::LDT + eb_] = gv1;
-        }
-        ea_ += qa;
-        eb_ += qb;
-        if (eb_ >= d) {
-          eb_ -= d;
-          ++ea_;
-        }
-      }
-      __syncthreads();
-#pragma unroll
-      for (int tj = 0; tj < NT; ++tj) {
-        f32x4 v0 = f32x4{0.f, 0.f, 0.f, 0.f}, v1 = v0;
-        if (a < d && 16 * tj < d) {
-          v0 = *reinterpret_cast<const f32x4*>(G0 + a * G::LDT + 16 * tj + b0);
-          v1 = *reinterpret_cast<const f32x4*>(G1 + a * G::LDT + 16 * tj + b0);
-          if (16 * tj + 16 > d) {  // (wave-uniform: the tile that holds column d - 1; columns beyond hold stale LDS)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              const bool in = b0 + 16 * tj + i < d;
-              v0[i] = in ? v0[i] : 0.f;
-              v1[i] = in ? v1[i] : 0.f;
-            }
+  // soft graphs of both chains of the pair in element order, handed to the owning lanes through LDS (see k_acyc_hf)
+  {
+    const int sa = unit;
+    float* const G0 = reinterpret_cast<float*>(sb);
+    float* const G1 = reinterpret_cast<float*>(sb + G::IMG_STRIDE);
+    const int ndd = (int)dd, ndraw = (ndd + G::NTHR - 1) / G::NTHR;
+    const int qa = G::NTHR / d, qb = G::NTHR - qa * d;
+    int ea_ = tid / d, eb_ = tid - ea_ * d;
+    float s_next = tid < ndd ? sm[tid] : 0.f;
+    const uint32_t cbase = (uint32_t)((uint64_t)sa * dd), chalf = (uint32_t)(nbits >> 1);
+    for (int k = 0; k < ndraw; ++k) {
+      const int e = tid + G::NTHR * k;
+      const float s_cur = s_next;
+      s_next = e + G::NTHR < ndd ? sm[e + G::NTHR] : 0.f;
+      if (e < ndd) {
+        float gv0 = 0.f, gv1 = 0.f;
+        if (ea_ != eb_) {
+          const float ea = fast ? s_cur : alpha * s_cur;
+          uint32_t y0, y1;
+          threefry2x32_uh(tk, (uint32_t)tid, cbase + (uint32_t)(G::NTHR * k), chalf, y0, y1);  // counter cbase + e: only tid is the lane's
+          if (fast) {
+            const float u0 = rng_uniform(y0, ulo, 1.0f), u1 = rng_uniform(y1, ulo, 1.0f);
+            const float den0 = fmaf(1.0f - u0, ea, u0), den1 = fmaf(1.0f - u1, ea, u1);
+            gv0 = den0 == u0 ? 1.0f : u0 * __builtin_amdgcn_rcpf(den0);   // (saturated edges give exactly 1: see k_acyc_bf)
+            gv1 = den1 == u1 ? 1.0f : u1 * __builtin_amdgcn_rcpf(den1);
+          } else {
+            gv0 = 1.0f / (1.0f + expf(-tau * (rng_logistic(y0, tiny) + ea)));
+            gv1 = 1.0f / (1.0f + expf(-tau * (rng_logistic(y1, tiny) + ea)));
           }
         }
-        g[tj] = v0;
-        gnext[tj] = v1;
+        G0[ea_ * G::LDT + eb_] = gv0;
+        G1[ea_ * G::LDT + eb_] = gv1;
       }
-      __syncthreads();
-      // rows 16 NT .. KROWS - 1 of every column tile (odd NT: the second half of the last k-step) are zero in both images: the float
-      // staging areas above / below covered them
-      if (NT & 1) {
-        for (int e = tid; e < 2 * 2 * NT * 64; e += G::NTHR) {  // [image][piece][tile]: 16 rows x 32 bytes = 64 x 8 bytes
-          const int q8 = e & 63, t3 = e >> 6, tile = t3 % NT, pi = (t3 / NT) & 1, im = t3 / (2 * NT);
-          *reinterpret_cast<abf_u32x2*>(sb + im * G::IMG_STRIDE + pi * G::PIECE_BYTES + tile * G::TILE_BYTES + 16 * NT * 32 + q8 * 8) = abf_u32x2{0u, 0u};
-        }
+      ea_ += qa;
+      eb_ += qb;
+      if (eb_ >= d) {
+        eb_ -= d;
+        ++ea_;
       }
     }
-    for (int hf = 0; hf < 2; ++hf) {
-      if (hf == 1) {
+    __syncthreads();
 #pragma unroll
-        for (int tj = 0; tj < NT; ++tj) g[tj] = gnext[tj];
+    for (int tj = 0; tj < NT; ++tj) {
+      f32x4 v0 = f32x4{0.f, 0.f, 0.f, 0.f}, v1 = v0;
+      if (a < d && 16 * tj < d) {
+        v0 = *reinterpret_cast<const f32x4*>(G0 + a * G::LDT + 16 * tj + b0);
+        v1 = *reinterpret_cast<const f32x4*>(G1 + a * G::LDT + 16 * tj + b0);
+        if (16 * tj + 16 > d) {  // (wave-uniform: the tile that holds column d - 1; columns beyond hold stale LDS)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const bool in = b0 + 16 * tj + i < d;
+            v0[i] = in ? v0[i] : 0.f;
+            v1[i] = in ? v1[i] : 0.f;
+          }
+        }
       }
-      AhfwFrag<NT> A;
-      f32x4 acc[NT];
-      abfw_m0<NT>(g, acc, a, b0, d, inv_d);
-      ahfw_make_frag<NT>(acc, s0, A);
-      int cur = 0, E = AHF_E0, exP = AHF_E0, Eacc = 0;
-      ahfw_store_image<NT>(sb, wr_off, A);
-      __syncthreads();
-      const int ex = d - 1;
-      const int hb = 31 - __builtin_clz((unsigned)ex);
-      for (int bit = hb - 1; bit >= 0; --bit) {
-        const bool mult = (ex >> bit) & 1, last_sq = bit == 0 && !mult;
-        AhfwSteps<NT, 0>::run(acc, A, sb + cur, rd_off);  // P <- P P : acc = P^2 2^(2E) <= 128 max^2 < 2^(2 exP + 9)
-        cur ^= G::IMG_STRIDE;
-        Eacc = 2 * E;
-        if (!last_sq) {
-          {
-            const int sh = 6 - 2 * exP;  // stored pieces < 2^15
+      g[tj] = v0;
+      gnext[tj] = v1;
+    }
+    __syncthreads();
+    // rows 16 NT .. KROWS - 1 of every column tile (odd NT: the second half of the last k-step) are zero in both images: the float
+    // staging areas above / below covered them
+    if (NT & 1) {
+      for (int e = tid; e < 2 * 2 * NT * 64; e += G::NTHR) {  // [image][piece][tile]: 16 rows x 32 bytes = 64 x 8 bytes
+        const int q8 = e & 63, t3 = e >> 6, tile = t3 % NT, pi = (t3 / NT) & 1, im = t3 / (2 * NT);
+        *reinterpret_cast<abf_u32x2*>(sb + im * G::IMG_STRIDE + pi * G::PIECE_BYTES + tile * G::TILE_BYTES + 16 * NT * 32 + q8 * 8) = abf_u32x2{0u, 0u};
+      }
+    }
+  }
+  for (int hf = 0; hf < 2; ++hf) {
+    if (hf == 1) {
+#pragma unroll
+      for (int tj = 0; tj < NT; ++tj) g[tj] = gnext[tj];
+    }
+    AhfwFrag<NT> A;
+    f32x4 acc[NT];
+    abfw_m0<NT>(g, acc, a, b0, d, inv_d);
+    ahfw_make_frag<NT>(acc, s0, A);
+    int cur = 0, E = AHF_E0, exP = AHF_E0, Eacc = 0;
+    ahfw_store_image<NT>(sb, wr_off, A);
+    __syncthreads();
+    const int ex = d - 1;
+    const int hb = 31 - __builtin_clz((unsigned)ex);
+    for (int bit = hb - 1; bit >= 0; --bit) {
+      const bool mult = (ex >> bit) & 1, last_sq = bit == 0 && !mult;
+      AhfwSteps<NT, 0>::run(acc, A, sb + cur, rd_off);  // P <- P P : acc = P^2 2^(2E) <= 128 max^2 < 2^(2 exP + 9)
+      cur ^= G::IMG_STRIDE;
+      Eacc = 2 * E;
+      if (!last_sq) {
+        {
+          const int sh = 6 - 2 * exP;  // stored pieces < 2^15
+          const uint32_t wm = ahf_wave_max<NT>(acc);
+          if (lane == 0) slots[par * 8 + wave] = wm;
+          ahfw_make_frag<NT>(acc, ahf_pow2(sh), A);
+          ahfw_store_image<NT>(sb + cur, wr_off, A);
+          __syncthreads();
+          uint32_t mx = 0u;
+#pragma unroll
+          for (int w8 = 0; w8 < NT; ++w8) {
+            const uint32_t q = slots[par * 8 + w8];
+            mx = q > mx ? q : mx;
+          }
+          mx = __builtin_amdgcn_readfirstlane(mx);
+          E = Eacc + sh;
+          exP = (int)(mx >> 23) - 127 + sh;
+          par ^= 1;
+        }
+        if (mult) {  // P <- M P : acc = (M 2^14)(P 2^E) < 2^14 2 max < 2^(exP + 16)
+          f32x4 mv[NT];
+          AhfwFrag<NT> A0;
+          abfw_m0<NT>(g, mv, a, b0, d, inv_d);
+          ahfw_make_frag<NT>(mv, s0, A0);
+          AhfwSteps<NT, 0>::run(acc, A0, sb + cur, rd_off);
+          cur ^= G::IMG_STRIDE;
+          Eacc = AHF_E0 + E;
+          if (bit != 0) {
+            const int sh = -1 - exP;
             const uint32_t wm = ahf_wave_max<NT>(acc);
             if (lane == 0) slots[par * 8 + wave] = wm;
             ahfw_make_frag<NT>(acc, ahf_pow2(sh), A);
@@ -753,61 +766,34 @@ __global__ __launch_bounds__(64 * NT) void k_acyc_hfw(const float* __restrict__ 
             exP = (int)(mx >> 23) - 127 + sh;
             par ^= 1;
           }
-          if (mult) {  // P <- M P : acc = (M 2^14)(P 2^E) < 2^14 2 max < 2^(exP + 16)
-            f32x4 mv[NT];
-            AhfwFrag<NT> A0;
-            abfw_m0<NT>(g, mv, a, b0, d, inv_d);
-            ahfw_make_frag<NT>(mv, s0, A0);
-            AhfwSteps<NT, 0>::run(acc, A0, sb + cur, rd_off);
-            cur ^= G::IMG_STRIDE;
-            Eacc = AHF_E0 + E;
-            if (bit != 0) {
-              const int sh = -1 - exP;
-              const uint32_t wm = ahf_wave_max<NT>(acc);
-              if (lane == 0) slots[par * 8 + wave] = wm;
-              ahfw_make_frag<NT>(acc, ahf_pow2(sh), A);
-              ahfw_store_image<NT>(sb + cur, wr_off, A);
-              __syncthreads();
-              uint32_t mx = 0u;
-#pragma unroll
-              for (int w8 = 0; w8 < NT; ++w8) {
-                const uint32_t q = slots[par * 8 + w8];
-                mx = q > mx ? q : mx;
-              }
-              mx = __builtin_amdgcn_readfirstlane(mx);
-              E = Eacc + sh;
-              exP = (int)(mx >> 23) - 127 + sh;
-              par ^= 1;
-            }
-          }
         }
       }
-      float* T = reinterpret_cast<float*>(sb + cur);
+    }
+    float* T = reinterpret_cast<float*>(sb + cur);
 #pragma unroll
-      for (int tj = 0; tj < NT; ++tj) *reinterpret_cast<f32x4*>(T + a * G::LDT + 16 * tj + b0) = acc[tj];
-      __syncthreads();
-      // (first-order compensation of the pipe's truncation bias: every product level of the 3 x 32-term f16 dot products loses ~1.15e-7
-      //  relative, always downwards, which repeated squaring turns into -(d - 1) 1.15e-7 on M^(d-1) -- measured against the f32-MFMA
-      //  kernel at d = 80: mean -1.0e-5 / -8.2e-6 over the entries at alpha = 1000 / 20, spread 1e-6; with the factor the difference of
-      //  the two kernels is their rounding noise.  tests: test_acyclicity_f16_pipe_worst_cases)
-      const float ta = ldexpf(tau * alpha * (1.0f + 1.15e-7f * (float)(d - 1)), -Eacc);
+    for (int tj = 0; tj < NT; ++tj) *reinterpret_cast<f32x4*>(T + a * G::LDT + 16 * tj + b0) = acc[tj];
+    __syncthreads();
+    // (first-order compensation of the pipe's truncation bias: every product level of the 3 x 32-term f16 dot products loses ~1.15e-7
+    //  relative, always downwards, which repeated squaring turns into -(d - 1) 1.15e-7 on M^(d-1) -- measured against the f32-MFMA
+    //  kernel at d = 80: mean -1.0e-5 / -8.2e-6 over the entries at alpha = 1000 / 20, spread 1e-6; with the factor the difference of
+    //  the two kernels is their rounding noise.  tests: test_acyclicity_f16_pipe_worst_cases)
+    const float ta = ldexpf(tau * alpha * (1.0f + 1.15e-7f * (float)(d - 1)), -Eacc);
 #pragma unroll
-      for (int tj = 0; tj < NT; ++tj)
+    for (int tj = 0; tj < NT; ++tj)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int b = b0 + 16 * tj + i;
-          const float gv = g[tj][i];
-          out[tj][i] += T[b * G::LDT + a] * (ta * gv * (1.0f - gv));
-        }
-      __syncthreads();
-      if ((NT & 1) && hf == 0) {  // (the staging rows covered the zero rows of that image: restore them before the next chain's products)
-        const int im = cur ? 1 : 0;
-        for (int e = tid; e < 2 * NT * 64; e += G::NTHR) {
-          const int q8 = e & 63, t3 = e >> 6, tile = t3 % NT, pi = t3 / NT;
-          *reinterpret_cast<abf_u32x2*>(sb + im * G::IMG_STRIDE + pi * G::PIECE_BYTES + tile * G::TILE_BYTES + 16 * NT * 32 + q8 * 8) = abf_u32x2{0u, 0u};
-        }
-        // (ordered before the first read of those rows by the barrier after the next chain's first image store)
+      for (int i = 0; i < 4; ++i) {
+        const int b = b0 + 16 * tj + i;
+        const float gv = g[tj][i];
+        out[tj][i] += T[b * G::LDT + a] * (ta * gv * (1.0f - gv));
       }
+    __syncthreads();
+    if ((NT & 1) && hf == 0) {  // (the staging rows covered the zero rows of that image: restore them before the next chain's products)
+      const int im = cur ? 1 : 0;
+      for (int e = tid; e < 2 * NT * 64; e += G::NTHR) {
+        const int q8 = e & 63, t3 = e >> 6, tile = t3 % NT, pi = t3 / NT;
+        *reinterpret_cast<abf_u32x2*>(sb + im * G::IMG_STRIDE + pi * G::PIECE_BYTES + tile * G::TILE_BYTES + 16 * NT * 32 + q8 * 8) = abf_u32x2{0u, 0u};
+      }
+      // (ordered before the first read of those rows by the barrier after the next chain's first image store)
     }
   }
   if (a < d) {

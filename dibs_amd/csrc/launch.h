@@ -31,11 +31,12 @@ void bge_launch_sum_nodes(hipStream_t stream, const double* node_scores, float* 
 struct AcycLaunch {
   hipStream_t stream;
   const float* scores;
-  float* part;            // [Mloc][nblk][d*d] partial sums of the blocks
+  float* part;            // [Mloc][units][d*d] partial sums of the blocks (one unit each)
   float* w_acyc;          // [Mloc][d*d] mean over the chains (k_acyc_reduce, same stream)
   float* big;             // n_vars > 112: acyc_big_elems() floats (matrix powers through global memory); null otherwise
   Key2 carry;
-  int m0, M, Mloc, d, Sa, cpb, units, nblk;  // units != Sa: chains are taken in Threefry pairs
+  int m0, M, Mloc, d, Sa, units;  // units = blocks per particle: Sa / 2 Threefry pairs of chains (paired), else Sa chains
+  bool paired;
   float alpha, tau;
   int layout, tiny;
   hipEvent_t ev_start, ev_stop;  // profiling: kernel-level start / stop time stamps of the matrix-power kernel (see acyc_power_takes_events); else null

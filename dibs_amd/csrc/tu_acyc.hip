@@ -12,16 +12,15 @@ template <int NT>
 static void launch_nt(const AcycLaunch& a) {
   constexpr int DP = 16 * NT, LD = DP + 4;
   size_t lds = (size_t)(3 * DP + 1) * LD * 4;  // + one slack row (the k pipeline may load one step past the end)
-  const bool paired = a.units != a.Sa;
-  const dim3 grid(a.nblk, a.Mloc);
-  if (paired) {
+  const dim3 grid(a.units, a.Mloc);
+  if (a.paired) {
     dibs_allow_lds((const void*)k_acyc<NT, true>, lds);
-    hipLaunchKernelGGL((k_acyc<NT, true>), grid, dim3(256), lds, a.stream, a.scores, a.part, a.carry, a.m0, a.M, a.d, a.Sa, a.cpb, a.alpha,
-                       a.tau, a.layout, a.tiny, a.nblk);
+    hipLaunchKernelGGL((k_acyc<NT, true>), grid, dim3(256), lds, a.stream, a.scores, a.part, a.carry, a.m0, a.M, a.d, a.Sa, a.alpha, a.tau,
+                       a.layout, a.tiny);
   } else {
     dibs_allow_lds((const void*)k_acyc<NT, false>, lds);
-    hipLaunchKernelGGL((k_acyc<NT, false>), grid, dim3(256), lds, a.stream, a.scores, a.part, a.carry, a.m0, a.M, a.d, a.Sa, a.cpb, a.alpha,
-                       a.tau, a.layout, a.tiny, a.nblk);
+    hipLaunchKernelGGL((k_acyc<NT, false>), grid, dim3(256), lds, a.stream, a.scores, a.part, a.carry, a.m0, a.M, a.d, a.Sa, a.alpha, a.tau,
+                       a.layout, a.tiny);
   }
 }
 
@@ -29,26 +28,39 @@ static void launch_nt(const AcycLaunch& a) {
 // a.pipe == DIBS_PIPE_F32 keeps the f32-MFMA kernel (tuning.h: A/B runs)
 // (d <= 32 stays on k_acyc<NT>: measured at config 2 (d = 20, 32 particles) the 64-padded k_acyc_hf takes 17.4 us against 14.3 us for
 //  k_acyc<2> -- its element-order draws do not make up for products that are 3 x 3 instead of 2 x 2 tiles)
-static bool acyc_use_bf16(const AcycLaunch& a) { return a.pipe != DIBS_PIPE_F32 && a.units != a.Sa && a.d >= 33 && a.d <= 64; }
+static bool acyc_use_bf16(const AcycLaunch& a) { return a.pipe != DIBS_PIPE_F32 && a.paired && a.d >= 33 && a.d <= 64; }
 // 65 <= d <= 112 with paired chains: the same schemes with NT = 5 .. 7 tiles and waves (k_acyc_hfw / k_acyc_bfw)
-static bool acyc_use_bfw(const AcycLaunch& a) { return a.pipe != DIBS_PIPE_F32 && a.units != a.Sa && a.d > 64 && a.d <= 112; }
+static bool acyc_use_bfw(const AcycLaunch& a) { return a.pipe != DIBS_PIPE_F32 && a.paired && a.d > 64 && a.d <= 112; }
+// k_acyc_hf or k_acyc_bf (acyc_use_bf16), stamped with a.ev_start / a.ev_stop when given (acyc_power_takes_events); src: the kernel's score
+// arguments
+template <typename K, typename... Src>
+static void launch_bf(const AcycLaunch& a, K kernel, size_t lds, Src... src) {
+  const dim3 grid(a.units, (a.Mloc + 7) & ~7);
+  dibs_allow_lds((const void*)kernel, lds);
+  if (a.ev_start)
+    hipExtLaunchKernelGGL(kernel, grid, dim3(256), (uint32_t)lds, a.stream, a.ev_start, a.ev_stop, 0u, src..., a.part, a.carry, a.m0, a.M, a.Mloc,
+                          a.d, a.Sa, a.alpha, a.tau, a.layout, a.tiny);
+  else
+    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, a.stream, src..., a.part, a.carry, a.m0, a.M, a.Mloc, a.d, a.Sa, a.alpha, a.tau, a.layout,
+                       a.tiny);
+}
 // two-piece f16 operands for 65 <= d <= 112 (k_acyc_hfw, kernels_acyc_f16.h): the default of the whole range.  k_acyc_bfw runs only with
 // DIBS_ACYC_BF16=1 (A/B runs) or above a.hfw_max (DIBS_ACYC_HFW_MAX, default 112: nowhere; tests/hparam_states.py sets 80 to reach it)
 template <int NT>
 static void launch_hfw(const AcycLaunch& a) {
   const size_t lds = ahfw_lds_bytes(NT);
-  const dim3 grid(a.nblk, (a.Mloc + 7) & ~7);
+  const dim3 grid(a.units, (a.Mloc + 7) & ~7);
   dibs_allow_lds((const void*)k_acyc_hfw<NT>, lds);
-  hipLaunchKernelGGL(k_acyc_hfw<NT>, grid, dim3(64 * NT), lds, a.stream, a.scores, a.eas, a.part, a.carry, a.m0, a.M, a.Mloc, a.d, a.Sa, a.cpb, a.alpha,
-                     a.tau, a.layout, a.tiny, a.nblk);
+  hipLaunchKernelGGL(k_acyc_hfw<NT>, grid, dim3(64 * NT), lds, a.stream, a.scores, a.eas, a.part, a.carry, a.m0, a.M, a.Mloc, a.d, a.Sa, a.alpha, a.tau,
+                     a.layout, a.tiny);
 }
 template <int NT>
 static void launch_bfw(const AcycLaunch& a) {
   const size_t lds = abfw_lds_bytes(NT);
-  const dim3 grid(a.nblk, (a.Mloc + 7) & ~7);
+  const dim3 grid(a.units, (a.Mloc + 7) & ~7);
   dibs_allow_lds((const void*)k_acyc_bfw<NT>, lds);
-  hipLaunchKernelGGL(k_acyc_bfw<NT>, grid, dim3(64 * NT), lds, a.stream, a.scores, a.part, a.carry, a.m0, a.M, a.Mloc, a.d, a.Sa, a.cpb, a.alpha,
-                     a.tau, a.layout, a.tiny, a.nblk);
+  hipLaunchKernelGGL(k_acyc_bfw<NT>, grid, dim3(64 * NT), lds, a.stream, a.scores, a.part, a.carry, a.m0, a.M, a.Mloc, a.d, a.Sa, a.alpha, a.tau,
+                     a.layout, a.tiny);
 }
 
 // n_vars > 112: matrices in global memory (kernels_acyc_big.h); a.big = three [Mloc * Sa][dp][dp] buffers
@@ -86,7 +98,7 @@ static void acyc_big_launch(const AcycLaunch& a) {
 void acyc_launch_reduce(const AcycLaunch& a) {
   if (a.big) return;
   const int dd = a.d * a.d;
-  hipLaunchKernelGGL(k_acyc_reduce, dim3(a.Mloc, (dd + 255) / 256), dim3(256), 0, a.stream, a.part, a.w_acyc, a.nblk, dd, 1.0f / (float)a.Sa);
+  hipLaunchKernelGGL(k_acyc_reduce, dim3(a.Mloc, (dd + 255) / 256), dim3(256), 0, a.stream, a.part, a.w_acyc, a.units, dd, 1.0f / (float)a.Sa);
 }
 bool acyc_power_takes_events(const AcycLaunch& a) { return !a.big && acyc_use_bf16(a); }
 void acyc_launch_power(const AcycLaunch& a) {
@@ -96,30 +108,9 @@ void acyc_launch_power(const AcycLaunch& a) {
   }
   if (acyc_use_bf16(a)) {
     // two-piece f16 operands (kernels_acyc_f16.h: half the matrix instructions); DIBS_PIPE_BF16: the three-piece bf16 kernel (A/B runs)
-    const bool bf16 = a.pipe == DIBS_PIPE_BF16;
-    const size_t lds = bf16 ? (size_t)2 * ABF_IMG_BYTES : (size_t)AHF_LDS_BYTES;
-    const dim3 grid(a.nblk, (a.Mloc + 7) & ~7);
-#define ACYC_BF_LAUNCH(KERNEL_)                                                                                                            \
-    {                                                                                                                                        \
-      dibs_allow_lds((const void*)KERNEL_, lds);                                                                                             \
-      if (a.ev_start)                                                                                                                        \
-        hipExtLaunchKernelGGL(KERNEL_, grid, dim3(256), (uint32_t)lds, a.stream, a.ev_start, a.ev_stop, 0u, ACYC_SRC, a.part, a.carry,       \
-                              a.m0, a.M, a.Mloc, a.d, a.Sa, a.cpb, a.alpha, a.tau, a.layout, a.tiny, a.nblk);                                  \
-      else                                                                                                                                   \
-        hipLaunchKernelGGL(KERNEL_, grid, dim3(256), lds, a.stream, ACYC_SRC, a.part, a.carry, a.m0, a.M, a.Mloc, a.d, a.Sa, a.cpb,            \
-                           a.alpha, a.tau, a.layout, a.tiny, a.nblk);                                                                          \
-    }
-#define ACYC_SRC a.scores
-    if (bf16) {
-      if (a.d > 48) ACYC_BF_LAUNCH(k_acyc_bf<true>) else ACYC_BF_LAUNCH(k_acyc_bf<false>)
-    } else {
-#undef ACYC_SRC
-#define ACYC_SRC a.scores, a.eas
-      // three waves per SIMD (no spills, M's fragments kept)
-      if (a.d > 48) ACYC_BF_LAUNCH((k_acyc_hf<true, 3>)) else ACYC_BF_LAUNCH((k_acyc_hf<false, 3>))
-    }
-#undef ACYC_BF_LAUNCH
-#undef ACYC_SRC
+    // (k_acyc_hf at three waves per SIMD: no spills, M's fragments kept)
+    if (a.pipe == DIBS_PIPE_BF16) launch_bf(a, a.d > 48 ? k_acyc_bf<true> : k_acyc_bf<false>, (size_t)2 * ABF_IMG_BYTES, a.scores);
+    else launch_bf(a, a.d > 48 ? k_acyc_hf<true, 3> : k_acyc_hf<false, 3>, (size_t)AHF_LDS_BYTES, a.scores, a.eas);
     return;
   }
   if (acyc_use_bfw(a)) {

@@ -39,26 +39,26 @@ template <int NT>
 static void launch_nt_batch(const AcycLaunch& a, const ProblemHP* hp, int pM) {
   constexpr int DP = 16 * NT, LD = DP + 4;
   const size_t lds = (size_t)(3 * DP + 1) * LD * 4;
-  const dim3 grid(a.nblk, a.Mloc);
-  if (a.units != a.Sa) {
+  const dim3 grid(a.units, a.Mloc);
+  if (a.paired) {
     dibs_allow_lds((const void*)k_acyc_batch<NT, true>, lds);
-    hipLaunchKernelGGL((k_acyc_batch<NT, true>), grid, dim3(256), lds, a.stream, a.scores, a.part, a.carry, a.m0, a.M, a.d, a.Sa, a.cpb, hp, pM,
-                       a.tau, a.layout, a.tiny, a.nblk);
+    hipLaunchKernelGGL((k_acyc_batch<NT, true>), grid, dim3(256), lds, a.stream, a.scores, a.part, a.carry, a.m0, a.M, a.d, a.Sa, hp, pM, a.tau,
+                       a.layout, a.tiny);
   } else {
     dibs_allow_lds((const void*)k_acyc_batch<NT, false>, lds);
-    hipLaunchKernelGGL((k_acyc_batch<NT, false>), grid, dim3(256), lds, a.stream, a.scores, a.part, a.carry, a.m0, a.M, a.d, a.Sa, a.cpb, hp, pM,
-                       a.tau, a.layout, a.tiny, a.nblk);
+    hipLaunchKernelGGL((k_acyc_batch<NT, false>), grid, dim3(256), lds, a.stream, a.scores, a.part, a.carry, a.m0, a.M, a.d, a.Sa, hp, pM, a.tau,
+                       a.layout, a.tiny);
   }
 }
 template <bool FOUR>
 static void launch_hf_batch(const AcycLaunch& a, const ProblemHP* hp, int pM) {
   const size_t lds = (size_t)AHF_LDS_BYTES;
   dibs_allow_lds((const void*)k_acyc_hf_batch<FOUR, 3>, lds);
-  hipLaunchKernelGGL((k_acyc_hf_batch<FOUR, 3>), dim3(a.nblk, (a.Mloc + 7) & ~7), dim3(256), lds, a.stream, a.scores, a.eas, a.part, a.carry, a.m0,
-                     a.M, a.Mloc, a.d, a.Sa, a.cpb, hp, pM, a.tau, a.layout, a.tiny, a.nblk);
+  hipLaunchKernelGGL((k_acyc_hf_batch<FOUR, 3>), dim3(a.units, (a.Mloc + 7) & ~7), dim3(256), lds, a.stream, a.scores, a.eas, a.part, a.carry, a.m0,
+                     a.M, a.Mloc, a.d, a.Sa, hp, pM, a.tau, a.layout, a.tiny);
 }
 void batch_launch_acyc_power(const AcycLaunch& a, const ProblemHP* hp, int pM) {
-  if (a.pipe != DIBS_PIPE_F32 && a.units != a.Sa && a.d >= 33) {  // (acyc_use_bf16 of tu_acyc.hip; the bf16 pipe never comes here)
+  if (a.pipe != DIBS_PIPE_F32 && a.paired && a.d >= 33) {  // (acyc_use_bf16 of tu_acyc.hip; the bf16 pipe never comes here)
     if (a.d > 48) launch_hf_batch<true>(a, hp, pM);
     else launch_hf_batch<false>(a, hp, pM);
     return;

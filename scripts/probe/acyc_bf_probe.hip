@@ -24,7 +24,7 @@ static void mm(const std::vector<double>& a, const std::vector<double>& b, std::
 }
 
 static void run(int d, int Mloc, int Sa, float alpha, bool timing) {
-  const int cpb = 1, nblk = Sa / 2;
+  const int nblk = Sa / 2;  // one pair of chains per block
   std::vector<float> scores((size_t)Mloc * d * d);
   srand(7);
   for (auto& s : scores) s = 4.0f * ((float)rand() / RAND_MAX - 0.5f);
@@ -41,9 +41,9 @@ static void run(int d, int Mloc, int Sa, float alpha, bool timing) {
   hipFuncSetAttribute((const void*)k_acyc_bf<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
   Key2 carry{123u, 456u};
   const dim3 grid(nblk, Mloc);
-  hipLaunchKernelGGL((k_acyc<4, true>), grid, dim3(256), lds0, 0, ds, dp0, carry, 0, Mloc, d, Sa, cpb, alpha, 1.0f, 0, 0, nblk, LikArgs{});
-  if (d > 48) hipLaunchKernelGGL(k_acyc_bf<true>, dim3(nblk, (Mloc + 7) & ~7), dim3(256), lds1, 0, ds, dp1, carry, 0, Mloc, Mloc, d, Sa, cpb, alpha, 1.0f, 0, 0, nblk, LikArgs{});
-  else hipLaunchKernelGGL(k_acyc_bf<false>, dim3(nblk, (Mloc + 7) & ~7), dim3(256), lds1, 0, ds, dp1, carry, 0, Mloc, Mloc, d, Sa, cpb, alpha, 1.0f, 0, 0, nblk, LikArgs{});
+  hipLaunchKernelGGL((k_acyc<4, true>), grid, dim3(256), lds0, 0, ds, dp0, carry, 0, Mloc, d, Sa, alpha, 1.0f, 0, 0);
+  if (d > 48) hipLaunchKernelGGL(k_acyc_bf<true>, dim3(nblk, (Mloc + 7) & ~7), dim3(256), lds1, 0, ds, dp1, carry, 0, Mloc, Mloc, d, Sa, alpha, 1.0f, 0, 0);
+  else hipLaunchKernelGGL(k_acyc_bf<false>, dim3(nblk, (Mloc + 7) & ~7), dim3(256), lds1, 0, ds, dp1, carry, 0, Mloc, Mloc, d, Sa, alpha, 1.0f, 0, 0);
   hipError_t e2 = hipDeviceSynchronize();
   hipMemcpy(p0.data(), dp0, np * 4, hipMemcpyDeviceToHost);
   hipMemcpy(p1.data(), dp1, np * 4, hipMemcpyDeviceToHost);
@@ -81,9 +81,9 @@ static void run(int d, int Mloc, int Sa, float alpha, bool timing) {
       for (int rep = 0; rep < 5; ++rep) {
         hipEventRecord(a, 0);
         for (int it = 0; it < 10; ++it) {
-          if (which == 0) hipLaunchKernelGGL((k_acyc<4, true>), grid, dim3(256), lds0, 0, ds, dp0, carry, 0, Mloc, d, Sa, cpb, alpha, 1.0f, 0, 0, nblk, LikArgs{});
-          else if (d > 48) hipLaunchKernelGGL(k_acyc_bf<true>, dim3(nblk, (Mloc + 7) & ~7), dim3(256), lds1, 0, ds, dp1, carry, 0, Mloc, Mloc, d, Sa, cpb, alpha, 1.0f, 0, 0, nblk, LikArgs{});
-  else hipLaunchKernelGGL(k_acyc_bf<false>, dim3(nblk, (Mloc + 7) & ~7), dim3(256), lds1, 0, ds, dp1, carry, 0, Mloc, Mloc, d, Sa, cpb, alpha, 1.0f, 0, 0, nblk, LikArgs{});
+          if (which == 0) hipLaunchKernelGGL((k_acyc<4, true>), grid, dim3(256), lds0, 0, ds, dp0, carry, 0, Mloc, d, Sa, alpha, 1.0f, 0, 0);
+          else if (d > 48) hipLaunchKernelGGL(k_acyc_bf<true>, dim3(nblk, (Mloc + 7) & ~7), dim3(256), lds1, 0, ds, dp1, carry, 0, Mloc, Mloc, d, Sa, alpha, 1.0f, 0, 0);
+  else hipLaunchKernelGGL(k_acyc_bf<false>, dim3(nblk, (Mloc + 7) & ~7), dim3(256), lds1, 0, ds, dp1, carry, 0, Mloc, Mloc, d, Sa, alpha, 1.0f, 0, 0);
         }
         hipEventRecord(b, 0); hipEventSynchronize(b);
         float ms; hipEventElapsedTime(&ms, a, b); best = fminf(best, ms / 10);

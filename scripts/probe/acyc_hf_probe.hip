@@ -15,17 +15,17 @@ static void mm(const std::vector<double>& a, const std::vector<double>& b, std::
 
 static float* g_eas = nullptr;  // exp(-alpha scores), as k_edge_scores hands it to k_acyc_hf
 template <typename K>
-static void launch(K kern, size_t lds, int nblk, int Mloc, const float* ds, float* dp, Key2 carry, int d, int Sa, int cpb, float alpha) {
-  hipLaunchKernelGGL(kern, dim3(nblk, (Mloc + 7) & ~7), dim3(256), lds, 0, ds, dp, carry, 0, Mloc, Mloc, d, Sa, cpb, alpha, 1.0f, 0, 0, nblk);
+static void launch(K kern, size_t lds, int nblk, int Mloc, const float* ds, float* dp, Key2 carry, int d, int Sa, float alpha) {
+  hipLaunchKernelGGL(kern, dim3(nblk, (Mloc + 7) & ~7), dim3(256), lds, 0, ds, dp, carry, 0, Mloc, Mloc, d, Sa, alpha, 1.0f, 0, 0);
 }
 template <typename K>
-static void launch_hf(K kern, size_t lds, int nblk, int Mloc, const float* ds, float* dp, Key2 carry, int d, int Sa, int cpb, float alpha) {
-  hipLaunchKernelGGL(kern, dim3(nblk, (Mloc + 7) & ~7), dim3(256), lds, 0, ds, (const float*)g_eas, dp, carry, 0, Mloc, Mloc, d, Sa, cpb, alpha, 1.0f, 0, 0, nblk);
+static void launch_hf(K kern, size_t lds, int nblk, int Mloc, const float* ds, float* dp, Key2 carry, int d, int Sa, float alpha) {
+  hipLaunchKernelGGL(kern, dim3(nblk, (Mloc + 7) & ~7), dim3(256), lds, 0, ds, (const float*)g_eas, dp, carry, 0, Mloc, Mloc, d, Sa, alpha, 1.0f, 0, 0);
 }
 
 static int g_only = -1;  // >= 0: time only this variant (PMC runs)
-static void run(int d, int Mloc, int Sa, float alpha, float sscale, int cpb, bool timing) {
-  const int nblk = (Sa / 2 + cpb - 1) / cpb;
+static void run(int d, int Mloc, int Sa, float alpha, float sscale, bool timing) {
+  const int nblk = Sa / 2;  // one pair of chains per block
   std::vector<float> scores((size_t)Mloc * d * d);
   srand(7);
   for (auto& s : scores) s = sscale * 4.0f * ((float)rand() / RAND_MAX - 0.5f);
@@ -45,9 +45,9 @@ static void run(int d, int Mloc, int Sa, float alpha, float sscale, int cpb, boo
   hipFuncSetAttribute((const void*)k_acyc_bf<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bf);
   Key2 carry{123u, 456u};
   auto go = [&](int v) {
-    if (v == 0) { if (d > 48) launch(k_acyc_bf<true>, lds_bf, nblk, Mloc, ds, dp[0], carry, d, Sa, cpb, alpha); else launch(k_acyc_bf<false>, lds_bf, nblk, Mloc, ds, dp[0], carry, d, Sa, cpb, alpha); }
-    if (v == 1) { if (d > 48) launch_hf(k_acyc_hf<true, 3>, lds_hf, nblk, Mloc, ds, dp[1], carry, d, Sa, cpb, alpha); else launch_hf(k_acyc_hf<false, 3>, lds_hf, nblk, Mloc, ds, dp[1], carry, d, Sa, cpb, alpha); }
-    if (v == 2) { if (d > 48) launch_hf(k_acyc_hf<true, 4>, lds_hf, nblk, Mloc, ds, dp[2], carry, d, Sa, cpb, alpha); else launch_hf(k_acyc_hf<false, 4>, lds_hf, nblk, Mloc, ds, dp[2], carry, d, Sa, cpb, alpha); }
+    if (v == 0) { if (d > 48) launch(k_acyc_bf<true>, lds_bf, nblk, Mloc, ds, dp[0], carry, d, Sa, alpha); else launch(k_acyc_bf<false>, lds_bf, nblk, Mloc, ds, dp[0], carry, d, Sa, alpha); }
+    if (v == 1) { if (d > 48) launch_hf(k_acyc_hf<true, 3>, lds_hf, nblk, Mloc, ds, dp[1], carry, d, Sa, alpha); else launch_hf(k_acyc_hf<false, 3>, lds_hf, nblk, Mloc, ds, dp[1], carry, d, Sa, alpha); }
+    if (v == 2) { if (d > 48) launch_hf(k_acyc_hf<true, 4>, lds_hf, nblk, Mloc, ds, dp[2], carry, d, Sa, alpha); else launch_hf(k_acyc_hf<false, 4>, lds_hf, nblk, Mloc, ds, dp[2], carry, d, Sa, alpha); }
   };
   for (int v = 0; v < 3; ++v) go(v);
   hipError_t e2 = hipDeviceSynchronize();
@@ -91,8 +91,8 @@ static void run(int d, int Mloc, int Sa, float alpha, float sscale, int cpb, boo
       if (n) printf("   %s signed rel err: mean %+.3e  sd %.3e  (n=%d)\n", v ? "f16x2 " : "bf16x3", sum / n, sqrt(sum2 / n - (sum / n) * (sum / n)), n);
     }
   }
-  printf("d=%d Mloc=%d Sa=%d alpha=%g sscale=%g cpb=%d sync=%s max|ref|=%.3g\n   vs double, relative to max (elementwise): bf16x3 %.3g (%.3g) nan %d | f16x2 wpe3 %.3g (%.3g) nan %d | f16x2 wpe4 %.3g (%.3g) nan %d\n",
-         d, Mloc, Sa, alpha, sscale, cpb, hipGetErrorName(e2), maxref, e[0] / maxref, eel[0], nan[0], e[1] / maxref, eel[1], nan[1], e[2] / maxref, eel[2], nan[2]);
+  printf("d=%d Mloc=%d Sa=%d alpha=%g sscale=%g sync=%s max|ref|=%.3g\n   vs double, relative to max (elementwise): bf16x3 %.3g (%.3g) nan %d | f16x2 wpe3 %.3g (%.3g) nan %d | f16x2 wpe4 %.3g (%.3g) nan %d\n",
+         d, Mloc, Sa, alpha, sscale, hipGetErrorName(e2), maxref, e[0] / maxref, eel[0], nan[0], e[1] / maxref, eel[1], nan[1], e[2] / maxref, eel[2], nan[2]);
   if (timing) {
     hipEvent_t a, b; hipEventCreate(&a); hipEventCreate(&b);
     const char* names[3] = {"k_acyc_bf       ", "k_acyc_hf wpe 3 ", "k_acyc_hf wpe 4 "};
@@ -112,30 +112,29 @@ static void run(int d, int Mloc, int Sa, float alpha, float sscale, int cpb, boo
 }
 
 int main(int argc, char** argv) {
-  if (argc > 1) {  // acyc_hf_probe <variant 0..2> [d] [Mloc] [cpb]: headline grid only
+  if (argc > 1) {  // acyc_hf_probe <variant 0..2> [d] [Mloc]: headline grid only
     g_only = atoi(argv[1]);
-    run(argc > 2 ? atoi(argv[2]) : 50, argc > 3 ? atoi(argv[3]) : 128, 32, 0.05f, 1.f, argc > 4 ? atoi(argv[4]) : 1, true);
+    run(argc > 2 ? atoi(argv[2]) : 50, argc > 3 ? atoi(argv[3]) : 128, 32, 0.05f, 1.f, true);
     return 0;
   }
   hipFuncSetAttribute((const void*)k_acyc_hf<true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)AHF_LDS_BYTES);
-  run(50, 2, 4, 0.0f, 1.f, 1, false);
-  run(50, 2, 4, 0.5f, 1.f, 1, false);
-  run(50, 2, 4, 20.f, 1.f, 1, false);
-  run(50, 2, 4, 300.f, 1.f, 1, false);
-  run(50, 2, 4, 300.f, 0.02f, 1, false);
-  run(50, 2, 4, 2000.f, 1.f, 1, false);
-  run(64, 2, 4, 0.2f, 1.f, 1, false);
-  run(33, 1, 2, 0.2f, 1.f, 1, false);
-  run(48, 1, 2, 3.0f, 1.f, 1, false);
-  run(49, 1, 2, 3.0f, 1.f, 1, false);
-  run(60, 1, 2, 2.0f, 1.f, 1, false);
-  run(50, 3, 8, 1.0f, 1.f, 2, false);
-  run(50, 128, 32, 0.05f, 1.f, 1, true);
-  run(50, 128, 32, 10.f, 1.f, 1, true);
-  run(50, 128, 32, 0.05f, 1.f, 2, true);
-  run(40, 128, 32, 0.05f, 1.f, 1, true);
-  run(64, 128, 32, 0.05f, 1.f, 1, true);
-  run(50, 16, 32, 0.05f, 1.f, 1, true);
-  run(50, 1024, 32, 0.05f, 1.f, 1, true);
+  run(50, 2, 4, 0.0f, 1.f, false);
+  run(50, 2, 4, 0.5f, 1.f, false);
+  run(50, 2, 4, 20.f, 1.f, false);
+  run(50, 2, 4, 300.f, 1.f, false);
+  run(50, 2, 4, 300.f, 0.02f, false);
+  run(50, 2, 4, 2000.f, 1.f, false);
+  run(64, 2, 4, 0.2f, 1.f, false);
+  run(33, 1, 2, 0.2f, 1.f, false);
+  run(48, 1, 2, 3.0f, 1.f, false);
+  run(49, 1, 2, 3.0f, 1.f, false);
+  run(60, 1, 2, 2.0f, 1.f, false);
+  run(50, 3, 8, 1.0f, 1.f, false);
+  run(50, 128, 32, 0.05f, 1.f, true);
+  run(50, 128, 32, 10.f, 1.f, true);
+  run(40, 128, 32, 0.05f, 1.f, true);
+  run(64, 128, 32, 0.05f, 1.f, true);
+  run(50, 16, 32, 0.05f, 1.f, true);
+  run(50, 1024, 32, 0.05f, 1.f, true);
   return 0;
 }

@@ -8,12 +8,10 @@ two already restate (acyc_kernel, lin_kernel, nn_logprob_kernel, the stage bound
       sets staged in LDS or read from global memory.  k_bge_sample (kernels_bge.h): 64 lanes over S / 2 pairs or S samples.  The joint
       models: grad_softmax_stats<4> and k_soft_combine stride by 256, k_grad_plan by 64; the log-probability launchers cut S into blocks.
   Sa  k_acyc_reduce (kernels_acyc.h) adds the per-block partial sums in groups of 16 and a guarded tail; the grid of every acyclicity
-      kernel is acyc_nblk units wide.
+      kernel is acyc_units blocks wide (one unit per block).
 
 tests/test_sample_axis_host.py holds the table against the restatement and the reference against itself; tests/test_gpu_sample_axis.py
 runs the cases on the device."""
-import functools
-
 import numpy as np
 
 import hparam_states as H
@@ -136,36 +134,9 @@ def second_trip_samples(d, S, layout="legacy"):
 
 # ---- the acyclicity term: engine.hip, kernels_acyc.h ---------------------------------------------------------------------------------------
 def acyc_units(d, Sa, layout="legacy"):
-    """engine.hip: engine_alloc -- a work unit is a pair of chains where one Threefry call serves both (H.acyc_paired), else one chain"""
+    """engine.hip: engine_alloc -- a work unit is a pair of chains where one Threefry call serves both (H.acyc_paired), else one chain;
+    every acyclicity block handles one unit"""
     return Sa // 2 if H.acyc_paired(d, Sa, layout) else Sa
-
-
-@functools.lru_cache(maxsize=None)
-def cpb_search(units, M, slots):
-    """the loop itself: the first cpb in 1 .. units with the smallest ceil(ceil(units / cpb) M / slots) cpb"""
-    best, best_cost = 1, -1
-    for cpb in range(1, units + 1):
-        nblk = ((units + cpb - 1) // cpb) * M
-        cost = ((nblk + slots - 1) // slots) * cpb
-        if best_cost < 0 or cost < best_cost:
-            best_cost, best = cost, cpb
-    return best
-
-
-def acyc_slots(d):
-    """engine.hip: engine_alloc -- 256 CUs x resident blocks per CU (three LDS matrices each, at most 8)"""
-    dpad = (d + 15) & ~15
-    return 256 * min(max(1, LDS // ((3 * dpad + 1) * (dpad + 4) * 4)), 8)
-
-
-def acyc_cpb(d, M, Sa, layout="legacy"):
-    """engine.hip: engine_alloc, the `cpb` loop -- chains per block minimising ceil(ceil(U / k) M / slots) k, first minimum kept"""
-    return cpb_search(acyc_units(d, Sa, layout), M, acyc_slots(d))
-
-
-def acyc_nblk(d, M, Sa, layout="legacy"):
-    units, cpb = acyc_units(d, Sa, layout), acyc_cpb(d, M, Sa, layout)
-    return (units + cpb - 1) // cpb
 
 
 def reduce_trips(nblk):
@@ -224,7 +195,7 @@ def classify(c, nnz=None):
     """the set of branch names one step of the case runs.  nnz: the largest count of samples with non-zero float32 weight over the particles
     (from the float64 oracle); without it a case whose stage_cap is below S is `stage_by_nnz`."""
     d, S, Sa, M = c["d"], c["S"], c["Sa"], c["M"]
-    nblk = acyc_nblk(d, M, Sa, c["layout"])
+    nblk = acyc_units(d, Sa, c["layout"])
     out = {"acyc:" + H.acyc_family(H.acyc_kernel(d, Sa, c["layout"], c["hfw_max"]))}
     if d <= 112:
         out |= {"reduce:" + reduce_trips(nblk), "acyc_grid>16" if nblk > 16 else "acyc_grid<=16"}

@@ -1,10 +1,12 @@
 """The sample-axis table of tests/sample_axis.py on the CPU: that its rows reach every branch `classify` can name and the kernel each row is
-there for, that the restated chains-per-block search of engine_alloc never leaves 1, and that the REFERENCE of
+there for, that the grid of every acyclicity kernel is one block per unit wide, and that the REFERENCE of
 tests/test_gpu_sample_axis.py holds on its own -- the float32 C oracle stays within HALF of every stage bound of the float64 one on every
 row (the bounds do not ask float32 for the impossible at 1 000+ samples), the weighted sums really carry weight on the samples past a
 loop's first pass, the unstaged rows really have more non-zero weights than parent sets fit LDS, and every single acyclicity chain moves
 W_ACYC by 20 bounds or more.  The two refusals of dibs_engine_create that depend on S are read here too: the checks precede the first
 device call."""
+import hashlib
+
 import numpy as np
 import pytest
 
@@ -50,10 +52,18 @@ def test_the_table_reaches_every_branch_and_every_row_its_kernel(c_oracle64):
     assert len(set(IDS)) == len(IDS) and len(X.ALL_CASES) <= X.MAX_CASES
     assert sorted(map(X.case_id, X.ORACLE_CASES + X.BITWISE_CASES + X.F64_CASES + X.SOFT_CASES)) == sorted(IDS)     # every row is run by one GPU test
     classes = {X.case_id(c): X.classify(c, _nnz(c, c_oracle64)) for c in X.ALL_CASES}
+    # the case ids and the branches each reaches, as they stood while tests/sample_axis.py still restated engine_alloc's chains-per-block
+    # search (which could only return 1): sha256 of repr(sorted((id, sorted(branches))))
+    # (a failure prints the rows themselves: every id with the branches it reaches now)
+    rows = sorted((cid, sorted(cl)) for cid, cl in classes.items())
+    assert hashlib.sha256(repr(rows).encode()).hexdigest() == "64fb7919b35e807509885d8068255778afe042ced3960d210327e66cc2277500", rows
     seen = set().union(*classes.values())
     assert seen == X.BRANCHES, (sorted(X.BRANCHES - seen), sorted(seen - X.BRANCHES))
     for c in X.ALL_CASES:
         cl, cid = classes[X.case_id(c)], X.case_id(c)
+        if c["d"] <= 112:       # one unit per block: the grid of every acyclicity kernel, and k_acyc_reduce's sum, is acyc_units wide
+            units = X.acyc_units(c["d"], c["Sa"], c["layout"])
+            assert {"reduce:" + X.reduce_trips(units), "acyc_grid>16" if units > 16 else "acyc_grid<=16"} <= cl, (cid, cl)
         if c["group"] == "Sa":
             k = "k_acyc" if c["kernel"] == "k_acyc_batch" else c["kernel"]
             assert "acyc:" + k in cl and (c["d"] > 112 or "acyc_grid>16" in cl), (cid, cl)
@@ -82,18 +92,6 @@ def test_the_table_reaches_every_branch_and_every_row_its_kernel(c_oracle64):
     # the S = S_max row reads its parent sets unstaged at 8 variables as well: its cap is a third of S and its weights are flat
     top = next(c for c in X.BGE_CASES if c["S"] == X.bge_s_max(8))
     assert "unstaged" in classes[X.case_id(top)] and "idx_second_trip" in classes[X.case_id(top)]
-
-
-def test_chains_per_block_search_always_returns_one():
-    """FINDING (engine.hip, engine_alloc).  The search minimises cost(k) = ceil(ceil(U / k) M / slots) k.  ceil(U / k) >= U / k, so cost(k) >=
-    U M / slots, and cost(k) is an integer: cost(k) >= ceil(U M / slots) = cost(1).  The comparison is strict, so the first minimum, k = 1,
-    is kept: acyc_cpb is 1 and acyc_nblk == acyc_units for every size, and the multi-chain-per-block loops of the acyclicity kernels never
-    run.  Held here on the restated loop; a counter-example would be reported by this assertion."""
-    bad = [(d, M, Sa, lay) for lay in ("legacy", "partitionable") for d in range(2, 257) for M in (1, 2, 32, 128, 1024) for Sa in range(1, 257)
-           if X.acyc_cpb(d, M, Sa, lay) != 1]
-    assert not bad, bad[:10]
-    assert all(X.acyc_nblk(c["d"], c["M"], c["Sa"], c["layout"]) == X.acyc_units(c["d"], c["Sa"], c["layout"]) for c in X.ALL_CASES)
-    assert [X.acyc_slots(d) for d in (8, 20, 50, 80, 112)] == [2048, 2048, 768, 512, 256]      # (resident blocks per CU: 8, 8, 3, 2, 1)
 
 
 @pytest.mark.parametrize("case", C_CASES, ids=[X.case_id(c) for c in C_CASES])
