@@ -626,8 +626,8 @@ int carry_copy(dibs_engine* e, bool restore) {
 //    instantiations); one kernel matrix (latent).
 //  * chains: C chains of one joint model.  The data is shared, so every kernel that reads it runs unchanged over all rows; chain-aware are
 //    the keys, the two kernel matrices (latent -> kz, theta -> kt and kz + kt -> ksum) and phi (JOINT + BATCH forms).  With per-chain data
-//    (LinearGaussian, dibs_engine_set_data_problem for every chain) the step is the same: the launchers of tu_lin.hip take the per-chain
-//    forms of the data-reading kernels (tu_lin_chains.hip) when the workspace holds JointWork::n_chain_data data sets.
+//    (LinearGaussian, dibs_engine_set_data_problem for every chain) the step is the same: joint_lin_all_logprobs / joint_lin_all_grads take
+//    the launch text of lin_launch.h as compiled with the per-chain kernels (tu_lin_chains.hip) when JointWork::n_chain_data is set.
 // Hyper-parameters: per run, from the device table e->hp (ProblemHP; dibs_engine_set_problem_hparams / dibs_engine_set_chain_hparams, by
 // default the configuration's values in every row).  A batched engine's keys kernel forms this step's alpha and beta of every problem in
 // double, as the host does for a standalone engine; its kernel matrix and phi always read the table.  The edge, acyclicity and tail kernels

@@ -160,7 +160,7 @@ struct LinGramHost {  // one data set's Gram matrices on the host (joint_lin_gra
 void joint_lin_gram_host(LinGramHost* g, const float* x, const int32_t* mask, int N, int d);
 int joint_chain_gram_commit(JointWork* w, int d, const std::vector<LinGramHost>& chains);
 LinChainData joint_chain_data(const JointWork& w);
-// (the launchers return non-zero when a scratch area cannot be allocated: nothing was launched from that point on)
+// (the launchers return non-zero when a scratch area cannot be allocated: nothing was launched from that point on; lin_launch.h)
 int joint_lin_all_logprobs(JointWork* w, const JointLaunch& jl, Key2 carry_theta, Key2 carry_z);
 int joint_lin_all_grads(JointWork* w, const JointLaunch& jl, Key2 carry_theta, Key2 carry_z);
 // log p(theta_i, D | g_i) of n given (graph, parameter) pairs (held-out scoring; dibs_score_graphs)
@@ -168,20 +168,10 @@ int joint_lin_score_given(const JointWork& jw, const float* theta, const int32_t
                           float mean_edge, float sig_edge, hipStream_t stream);
 
 // ---- tu_lin_chains.hip: the per-chain forms of the six LinearGaussian kernel families (LinChainData) -----
-// Launched by tu_lin.hip's launchers in place of the shared-data kernel they chose, with the grid, LDS size and per-block counts they chose
-// (per = samples / pairs per block).  lin_chains_launch_*: nt = ceil(d / 16); epq, four: the instantiation tu_lin.hip picked
-struct LinGradJob;
-void lin_chains_launch_logprobs(int nt, dim3 grid, size_t lds, const LinChainData& cd, const JointLaunch& jl, float* lp, Key2 carry, int mode, int per);
-void lin_chains_launch_pair(int nt, int epq, dim3 grid, size_t lds, const LinChainData& cd, const JointLaunch& jl, float* lp, Key2 carry, int mode,
-                            int per);
-void lin_chains_launch_hf(int epq, bool four, dim3 grid, size_t lds, const LinChainData& cd, const JointLaunch& jl, float* lp, Key2 carry, int mode,
-                          int per);
-void lin_chains_launch_grad(int nt, dim3 grid, size_t lds, const LinChainData& cd, const JointLaunch& jl, const LinGradJob& jt, const LinGradJob& jz,
-                            const GradSplit& gs);
-void ling_chains_launch_logprobs(dim3 grid, size_t lds, const LinChainData& cd, int ng, const JointLaunch& jl, float* lp, Key2 carry, int mode,
-                                 float* ops_glob);
-void ling_chains_launch_grad(dim3 grid, size_t lds, const LinChainData& cd, int ng, const JointLaunch& jl, const LinGradJob& jt, const LinGradJob& jz,
-                             float* ops_glob, const GradSplit& gs);
+// The launch text of tu_lin.hip (lin_launch.h) compiled a second time: what joint_lin_all_logprobs / joint_lin_all_grads call for an engine
+// with per-chain data (JointWork::n_chain_data), and nothing else calls
+__attribute__((visibility("hidden"))) int lin_all_logprobs_chains(JointWork* w, const JointLaunch& jl, Key2 carry_theta, Key2 carry_z);
+__attribute__((visibility("hidden"))) int lin_all_grads_chains(JointWork* w, const JointLaunch& jl, Key2 carry_theta, Key2 carry_z);
 
 // ---- tu_nn.hip: JointDiBS + DenseNonlinearGaussian ---------------------------------------------------
 // true: the tuned one-hidden-layer kernels of kernels_nn.h apply; false: the general path of kernels_nn_generic.h runs

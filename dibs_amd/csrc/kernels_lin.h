@@ -18,8 +18,8 @@
 //                       below then spell out the parameters the kernels always had, and LIN_CHAIN_DATA is empty.
 //   tu_lin_chains.hip   a LinChainData (joint_launch.h): the kernels are named k_..._chains and LIN_CHAIN_DATA(m) derives x, mask and
 //                       any_mask of the chain of particle row m (m / M: block-uniform, scalar loads and a scalar offset).
-// One source text, so that the two forms cannot drift apart, and no wrapper around the shared-data kernels: as __forceinline__ blocks
-// under two __global__s the register allocation of k_lin_logprobs_pair and k_lin_grad changed.
+// One source text, so that the two forms cannot drift apart (and one launch text for it, lin_launch.h), and no wrapper around the kernels:
+// as __forceinline__ blocks under two __global__s the register allocation of k_lin_logprobs_pair and k_lin_grad changed.
 // The annealed alpha of a step and the baseline rate of the score-function estimator follow the data: launch arguments in tu_lin.hip
 // (LIN_ALPHA_PARAM / LIN_SFB_PARAM spell out `float alpha` / `double sf_baseline`), and in tu_lin_chains.hip locals of those names that
 // LIN_CHAIN_DATA / LIN_CHAIN_SFB take from the chain's row of the per-chain table (LinChainData::hp, dibs_engine_set_chain_hparams;

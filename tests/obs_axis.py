@@ -53,24 +53,29 @@ def joint_lin_fast_path(d, N, force_gram=False):
 
 
 def lin_paired(d, N, S, layout="legacy"):
-    """tu_lin.hip: joint_lin_logprobs, `paired` -- legacy PRNG layout, even S, S d d below 2^32, N <= 128"""
+    """lin_launch.h: lin_logprobs, `paired` -- legacy PRNG layout, even S, S d d below 2^32, N <= 128"""
     return layout == "legacy" and S % 2 == 0 and S * d * d < 0xFFFFFFFF and N <= 128
 
 
-def lin_kernel(d, N, S, layout="legacy"):
-    """tu_lin.hip: joint_lin_all_logprobs / joint_lin_logprobs -- which log-probability kernel a step launches"""
+def lin_kernel(d, N, S, layout="legacy", lin_f32=False):
+    """lin_launch.h: lin_all_logprobs / lin_logprobs -- which log-probability kernel a step launches, in either form of the data
+    (lin_f32: DIBS_LIN_F32, the `!jl.lin_f32` of use_bf)"""
     if not joint_lin_fast_path(d, N):
         return "gram"
     NT = (d + 15) // 16
     if not lin_paired(d, N, S, layout):
         return f"unpaired<{NT}>"
-    if NT <= 4 and d > 32:                      # use_bf (DIBS_LIN_F32 unset): LIN_HF_LAUNCH
+    if NT <= 4 and d > 32 and not lin_f32:      # use_bf: lin_launch_hf
         if d <= 48:
             return "hf<5,false>"
         return "hf<5,true>" if (d * d + 511) // 512 <= 5 else "hf<8,true>"
-    epq = (d * d + 255) // 256                  # LIN_PAIR_LAUNCH
-    if NT <= 4:
-        return f"pair<{NT},{4 if epq <= 4 else 10 if epq <= 10 else 16}>"
+    epq = (d * d + 255) // 256                  # lin_launch_pair: EPQ by NT; NT = 4 alone has two
+    if NT <= 2:
+        return f"pair<{NT},4>"
+    if NT == 3:
+        return "pair<3,10>"
+    if NT == 4:
+        return f"pair<4,{10 if epq <= 10 else 16}>"
     return f"pair<{NT},0>"
 
 
@@ -263,10 +268,16 @@ def _edge_table():
 
 
 LIN_CASES = _lin_table()
+# DIBS_LIN_F32=1 keeps the f32 paired kernels at 33 <= d <= 64, which no case above reaches: NT 3 (epq 7), the last size of pair<4,10>
+# (epq 10), the first of pair<4,16> (epq 11), and the operand exactly full (epq 16).  Not part of ALL_CASES: classify() restates the default
+LIN_F32_CASES = _alternate([_case("lingauss", d, 40) for d in (40, 50, 51, 64)])
+LIN_F32_KERNELS = ("pair<3,10>", "pair<4,10>", "pair<4,16>", "pair<4,16>")
 NN_CASES = _nn_table()
 EDGE_CASES = _edge_table()
 ALL_CASES = LIN_CASES + NN_CASES + EDGE_CASES
 
+# the paired classes that exist: NT = ceil(d / 16) and epq = ceil(d d / 256) are both functions of d (lin_launch.h instantiates these only)
+LIN_PAIR_CLASSES = ("pair<1,4>", "pair<2,4>", "pair<3,10>", "pair<4,10>", "pair<4,16>", "pair<5,0>", "pair<6,0>", "pair<7,0>")
 # every path / tile-count class that the table must visit (tests/test_obs_axis_host.py)
 LIN_KERNELS = ("pair<1,4>", "pair<2,4>", "hf<5,false>", "hf<5,true>", "hf<8,true>", "pair<5,0>", "pair<7,0>", "gram",
                "unpaired<1>", "unpaired<2>", "unpaired<3>", "unpaired<4>", "unpaired<5>", "unpaired<7>")

@@ -146,9 +146,9 @@ def reduce_trips(nblk):
     return (name + "+tail" if name and tail else name) or "tail"
 
 
-# ---- the joint models' launchers: tu_lin.hip, tu_nn.hip ---------------------------------------------------------------------------------------
+# ---- the joint models' launchers: lin_launch.h, tu_nn.hip -------------------------------------------------------------------------------------
 def lin_blocks(d, N, S, M, layout="legacy"):
-    """tu_lin.hip: joint_lin_logprobs -- (units, units per block) of the log-probability launch: pairs and ppb, or samples and spb = 4"""
+    """lin_launch.h: lin_logprobs -- (units, units per block) of the log-probability launch: pairs and ppb, or samples and spb = 4"""
     k = A.lin_kernel(d, N, S, layout)
     if k == "gram":
         return S, 1
@@ -174,7 +174,7 @@ def ragged(units, per_block):
 
 
 def gram_gx(S, rows):
-    """tu_lin.hip: the global-operand Gram path (n_vars > 198) clamps its grid to min(S, 1024 / rows) blocks that loop over the samples"""
+    """lin_launch.h, lin_all_logprobs: the global-operand Gram path (n_vars > 198) clamps its grid to min(S, 1024 / rows) blocks that loop over the samples"""
     return S if S < 1024 // rows else max(1024 // rows, 1)
 
 

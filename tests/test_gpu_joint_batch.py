@@ -121,7 +121,7 @@ def test_split_f16_tiers():
     _check(_lin(40, 8), _sets(40, 40, [1, 2]), [1, 2], [(0, 4)])   # k_lin_logprobs_hf<5, false, 8> (d <= 48)
 
 
-# lin_chains_launch_hf / _pair / _logprobs / _grad (tu_lin_chains.hip) repeat the instantiation switches of tu_lin.hip: one size per branch.
+# Both forms of the kernels are selected by one launch text (lin_launch.h, compiled in tu_lin.hip and tu_lin_chains.hip): one size per branch.
 #   d = 50: hf<5, true> (49 <= d, ceil(d d / 512) <= 5), d = 56: hf<8, true>; d = 72: NT = 5, the paired kernel with EPQ = 0 and k_lin_grad<5>;
 #   DIBS_LIN_F32=1 keeps the f32 paired kernel at 33 <= d <= 64: d = 40 has ceil(d d / 256) = 7 -> EPQ 10, d = 56 has 13 -> EPQ 16 (NT = 3, 4);
 #   d = 20 with odd S: the unpaired kernel and the gradient kernel at NT = 2.
@@ -182,7 +182,7 @@ def test_gram_path_single_matrix_read_through_the_caches(monkeypatch):
 
 def test_gram_path_global_operands_mixed_interventions():
     """d = 144 > 112 takes the Gram path by itself, and the gradient kernel keeps graph and masked weights in global scratch
-    (ling_ops_global: 8 d d + 128 > 159 KiB from d = 142); chain 0 has interventions (144 matrices), chain 1 its one matrix repeated.
+    (ling_shape, `glob`: 8 d d + 128 > 159 KiB from d = 142); chain 0 has interventions (144 matrices), chain 1 its one matrix repeated.
     One step of plain gradient descent at t = 1: from 128 variables on the acyclicity gradient of a fresh particle is ~1.5^(d - 1), and
     its square leaves float32 in RMSprop's second moment -- in the standalone engine and the reference alike (test_gpu_parity.py,
     test_joint_lingauss_gram_path) -- so an RMSprop run at this size has no finite state to compare; t = 0 would have alpha = beta = 0."""

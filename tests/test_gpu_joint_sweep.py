@@ -152,7 +152,7 @@ def test_all_fields_at_once(est, opt, prior):
 
 
 # ---- 3: every _chains instantiation reachable with n_vars <= 64 ------------------------------------------------------------------------
-# Read off joint_lin_logprobs / joint_lin_grads (tu_lin.hip) and batch_launch_acyc_power (tu_batch.hip), NT = ceil(d / 16) <= 4:
+# Read off lin_logprobs / lin_launch_pair / lin_launch_hf / lin_all_grads (lin_launch.h) and batch_launch_acyc_power (tu_batch.hip), NT = ceil(d / 16) <= 4:
 #   even S (legacy PRNG layout, N <= 128), d <= 32: k_lin_logprobs_pair_chains<1, 4> (d = 8), <2, 4> (d = 20: two tiles);
 #   33 <= d: k_lin_logprobs_hf_chains<5, false, 8> (d = 40), <5, true, 8> (d = 50: ceil(d d / 512) <= 5), <8, true, 8> (d = 56);
 #   DIBS_LIN_F32=1 keeps the paired f32 kernel there: <3, 10> (d = 40), <4, 10> (d = 50: ceil(d d / 256) = 10), <4, 16> (d = 56);

@@ -38,9 +38,10 @@ def _device_step(b):
         eng.close()
 
 
-def _assert_stages(case, b, dbg, after):
+def _assert_stages(case, b, dbg, after, ran=None):
+    """(ran: what to print as the case's class where the environment moves the engine off the path classify() restates)"""
     errs, keys_equal = A.stage_errors(b, dbg, after)
-    print(f"\n  obs_axis {b['id']} {A.classify(case)}: " + " ".join(f"{s}={e:.1e}" for s, e in errs.items()))
+    print(f"\n  obs_axis {b['id']} {ran or A.classify(case)}: " + " ".join(f"{s}={e:.1e}" for s, e in errs.items()))
     assert keys_equal                                                        # keys: bit for bit
     assert all(np.isfinite(v).all() for v in dbg.values())
     for s, e in errs.items():                                                # (in the order of the step: the first stage that is off is named)
@@ -54,6 +55,17 @@ def _assert_stages(case, b, dbg, after):
 def test_lingauss_stages_along_n(c_oracle64, case):
     b = A.built_case(case, c_oracle64)
     _assert_stages(case, b, *_device_step(b))
+
+
+@pytest.mark.parametrize("case,kernel", list(zip(A.LIN_F32_CASES, A.LIN_F32_KERNELS)), ids=[A.case_id(c) for c in A.LIN_F32_CASES])
+def test_lingauss_f32_paired_kernels(c_oracle64, monkeypatch, case, kernel):
+    """DIBS_LIN_F32=1: k_lin_logprobs_pair<3,10>, <4,10> and <4,16> (the f32-MFMA kernels that the split-f16 kernels replace at
+    33 <= d <= 64 by default) against the oracle, with the bounds of every other case.  Elsewhere they run in chains-versus-standalone
+    bit comparisons only, whose two sides take one selection (lin_launch.h)."""
+    monkeypatch.setenv("DIBS_LIN_F32", "1")
+    assert A.lin_kernel(case["d"], case["N"], case["S"], case["layout"], lin_f32=True) == kernel
+    b = A.built_case(case, c_oracle64)
+    _assert_stages(case, b, *_device_step(b), ran=("lingauss", f"DIBS_LIN_F32=1 {kernel}") + A.row_tiles(case["N"]))
 
 
 @pytest.mark.parametrize("case", A.NN_CASES, ids=[A.case_id(c) for c in A.NN_CASES])
@@ -136,7 +148,7 @@ def test_score_graphs_on_the_lds_path_after_a_gram_sized_set(c_oracle64, d):
     assert len(scoring._ENGINES) == 1
 
 
-# ---- per-chain data: the launchers of tu_lin_chains.hip at the same sizes -----------------------------------------------------------------
+# ---- per-chain data: the launch text of lin_launch.h as compiled in tu_lin_chains.hip, at the same sizes  --------------------------------
 STATE = ("z", "v_z", "theta", "v_theta", "baseline")
 CHUNKS = [(0, 3)]
 
@@ -174,7 +186,8 @@ def _batch(kw, datasets, keys):
 @pytest.mark.parametrize("d,N", A.CHAIN_CASES, ids=[f"d{d}-N{N}" for d, N in A.CHAIN_CASES])
 def test_per_chain_data_along_n(d, N):
     """three chains with a data set each (chain 1 with interventions, chains 0 and 2 without) end three steps bit-identical to three
-    standalone engines: lin_chains_launch_pair / _hf below 129 observations, _logprobs above, _grad at its largest LDS footprint"""
+    standalone engines: the per-chain paired / split-f16 kernels below 129 observations, the unpaired ones above, k_lin_grad_chains at its
+    largest LDS footprint"""
     N = A.lin_cut(d) if N == "cut" else N
     sets = [(A.structured_x(d, N, seed=11 + c), A.random_mask(d, N) if c == 1 else None) for c in range(3)]
     keys, kw = [61, 62, 63], _lin(d)

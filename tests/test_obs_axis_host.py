@@ -56,6 +56,23 @@ def test_every_case_is_in_exactly_one_class_and_every_class_is_visited():
         assert {(c["est"], bool(c["interv"])) for c in cs} == {(e, i) for e in ("reparam", "score") for i in (False, True)}
 
 
+def test_the_paired_classes_are_the_eight_that_are_instantiated():
+    """NT = ceil(d / 16) and epq = ceil(d d / 256) are both functions of d: over every size of the LDS-resident path, with the f16 kernels
+    and without them (lin_f32), a paired launch names one of eight (NT, EPQ) -- the ones lin_launch.h instantiates"""
+    seen = {A.lin_kernel(d, N, S, lin_f32=f32) for d in range(1, 113) for N in (1, 16, 17, 64, 112, 113, 128) for S in (2, 8, 16)
+            for f32 in (False, True)}
+    assert {k for k in seen if k.startswith("pair<")} == set(A.LIN_PAIR_CLASSES), seen
+    # the operand of a class covers every size of it: d d <= 256 EPQ (EPQ 0: no register-resident operand)
+    for d in range(1, 65):
+        k = A.lin_kernel(d, 16, 2, lin_f32=True)
+        assert d * d <= 256 * int(k[k.index(",") + 1:-1]), (d, k)
+    # without lin_f32 the f16 kernels take 33 <= d <= 64: the three f32 classes there are reached by DIBS_LIN_F32 only
+    assert {A.lin_kernel(d, 16, 2) for d in range(33, 65)} == {"hf<5,false>", "hf<5,true>", "hf<8,true>"}
+    assert {A.lin_kernel(d, 16, 2, lin_f32=True) for d in range(33, 65)} == {"pair<3,10>", "pair<4,10>", "pair<4,16>"}
+    assert tuple(A.lin_kernel(c["d"], c["N"], c["S"], lin_f32=True) for c in A.LIN_F32_CASES) == A.LIN_F32_KERNELS
+    assert [(c["d"] ** 2 + 255) // 256 for c in A.LIN_F32_CASES] == [7, 10, 11, 16] and all(c["S"] % 2 == 0 for c in A.LIN_F32_CASES)
+
+
 def test_intervention_edge_masks():
     for c in A.EDGE_CASES:
         m = A.make_mask(c)
