@@ -5,7 +5,7 @@ import ctypes as C
 ABI_VERSION = 2
 MAX_HIDDEN_LAYERS = 8
 
-LIK = {"bge": 0, "lingauss": 1, "densenn": 2}
+LIK = {"bge": 0, "lingauss": 1, "densenn": 2, "bdeu": 3}
 PRIOR = {"er": 0, "sf": 1, "uniform": 2, "edgewise": 3}
 EST = {"score": 0, "reparam": 1}
 OPT = {"gd": 0, "rmsprop": 1}
@@ -123,12 +123,12 @@ def make_config(*, n_vars, n_particles, n_observations, n_dim=None, joint=False,
                 logistic_minval_tiny=False, has_interventions=False, bge_alpha_mu=1.0, bge_alpha_lambd=None,
                 lin_obs_noise=0.1, lin_mean_edge=0.0, lin_sig_edge=1.0, lin_min_edge=0.5,
                 nn_hidden=(5,), nn_activation="relu", nn_bias=True, nn_obs_noise=0.1, nn_sig_param=1.0,
-                rank=0, n_ranks=1, device_id=0, n_problems=1, precision=32, n_chains=0):
+                rank=0, n_ranks=1, device_id=0, n_problems=1, precision=32, n_chains=0, bdeu_ess=1.0):
     """Build a dibs_config with the reference's defaults (svgd.py:60-83 marginal, :425-448 joint).  ``n_problems`` > 1: a batched
     engine of that many independent problems of ``n_particles`` particles each (include/dibs_hip.h, reserved_i[0]).  ``precision``
     64: the float64 engine (reserved_i[1]; 32 = float32, the default).  ``n_chains`` > 1: a chains engine of that many chains of one
     joint model on one data set, ``n_particles`` particles each (reserved_i[2]; 0 or 1: the standalone engine).  ``h_latent`` / ``h_theta``
-    ``"median"``: that kernel's bandwidth by the median heuristic, selected on the device every step (reserved_i[3])."""
+    ``"median"``: that kernel's bandwidth by the median heuristic, selected on the device every step (reserved_i[3]).  ``bdeu_ess``: the equivalent sample size of ``likelihood="bdeu"`` (reserved_d[0])."""
     c = DibsConfig()
     c.abi_version = ABI_VERSION
     c.n_vars = int(n_vars)
@@ -174,4 +174,6 @@ def make_config(*, n_vars, n_particles, n_observations, n_dim=None, joint=False,
     c.lin_obs_noise, c.lin_mean_edge = float(lin_obs_noise), float(lin_mean_edge)
     c.lin_sig_edge, c.lin_min_edge = float(lin_sig_edge), float(lin_min_edge)
     c.nn_obs_noise, c.nn_sig_param = float(nn_obs_noise), float(nn_sig_param)
+    if likelihood == "bdeu":
+        c.reserved_d[0] = float(bdeu_ess)
     return c

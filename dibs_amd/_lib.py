@@ -26,7 +26,7 @@ EXPORTS = [
     "dibs_engine_set_problem_hparams", "dibs_engine_get_problem_hparams",
     "dibs_engine_set_chain_hparams", "dibs_engine_get_chain_hparams", "dibs_engine_set_edge_prior",
     "dibs_engine_set_data_f64", "dibs_engine_set_state_f64", "dibs_engine_get_state_f64", "dibs_engine_precision",
-    "dibs_debug_threefry",
+    "dibs_debug_threefry", "dibs_engine_set_arities",
 ]
 
 
@@ -110,6 +110,7 @@ def load():
     lib.dibs_engine_set_chain_hparams.argtypes = [vp, i32, C.POINTER(ChainHparams)]
     lib.dibs_engine_get_chain_hparams.argtypes = [vp, i32, C.POINTER(ChainHparams)]
     lib.dibs_engine_set_edge_prior.argtypes = [vp, vp]
+    lib.dibs_engine_set_arities.argtypes = [vp, vp]
     lib.dibs_engine_set_data_f64.argtypes = [vp, vp, vp, vp]
     lib.dibs_engine_set_state_f64.argtypes = [vp] + [vp] * 6
     lib.dibs_engine_get_state_f64.argtypes = [vp] + [vp] * 6

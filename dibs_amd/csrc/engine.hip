@@ -181,7 +181,7 @@ static int engine_alloc(dibs_engine* e, const dibs_config& c, void* stream) {
   }
   HIP_OK(dalloc(&e->w_acyc, Ml * dd));
   {
-    const bool score_lik = c.likelihood == DIBS_LIK_BGE && c.grad_estimator_z == DIBS_EST_SCORE;
+    const bool score_lik = lik_marginal(c.likelihood) && c.grad_estimator_z == DIBS_EST_SCORE;
     const int ldz = tail_ldz(e->d, e->k, e->S, score_lik, LDS_LIMIT - 2048);
     if (tail_lds_bytes(e->d, ldz, e->S, e->W, score_lik, 0) > LDS_LIMIT - 2048) HIP_OK(dalloc(&e->w_tot, Ml * dd));
   }
@@ -233,7 +233,20 @@ static int engine_alloc(dibs_engine* e, const dibs_config& c, void* stream) {
   HIP_OK(dalloc(&e->phi_z, Ml * e->D));
   HIP_OK(dalloc(&e->phi_th, Ml * e->P));
   HIP_OK(dalloc(&e->counters, (size_t)DIBS_N_COUNTERS));
-  if (c.likelihood == DIBS_LIK_BGE) {
+  if (c.likelihood == DIBS_LIK_BDEU) {
+    // the sampling launch is BGe's (k_bge_sample): it reads a node's statistics for the closed form of an empty parent set and queues the
+    // rest.  Zero tables make that score 0 (N_j = 0); k_bdeu_nodes then writes every entry, and k_particle_grad resets the queue counters
+    e->bdeu = new BdeuState();
+    e->bdeu->log_ess = log(c.reserved_d[0] > 0 ? c.reserved_d[0] : 1.0);
+    const size_t dp = (size_t)e->d + 1;
+    HIP_OK(dalloc(&e->bge.Rp, 2 * dp * dp));
+    e->bge.Qp = e->bge.Rp + dp * dp;
+    HIP_OK(dalloc(&e->bge.gam, (size_t)e->d * dp));
+    HIP_OK(dalloc(&e->bge.Nj, (size_t)e->d));
+    HIP_OK(dalloc(&e->bge.ldR, (size_t)1));
+    e->bge.n_mats = 1;
+  }
+  if (lik_marginal(c.likelihood)) {
     HIP_OK(dalloc(&e->masks, Ml * e->S * e->d * e->W));
     HIP_OK(dalloc(&e->node_scores, Ml * e->S * e->d));
     e->bq.cap = (uint32_t)(Ml * e->S * e->d);
@@ -352,13 +365,22 @@ extern "C" int dibs_engine_create(const dibs_config* cfg, void* stream, dibs_eng
   if (c.grad_estimator_z != DIBS_EST_SCORE && c.grad_estimator_z != DIBS_EST_REPARAM)
     return fail("Unknown gradient estimator");  // dibs.py:318 (ValueError)
   if (c.optimizer != DIBS_OPT_GD && c.optimizer != DIBS_OPT_RMSPROP) return fail("unknown optimizer");  // svgd.py:122
-  if (c.likelihood < 0 || c.likelihood > 2) return fail("unknown likelihood model");
+  if (c.likelihood < 0 || c.likelihood > DIBS_LIK_BDEU) return fail("unknown likelihood model");
   if (c.graph_prior < 0 || c.graph_prior > DIBS_PRIOR_EDGEWISE) return fail("unknown graph prior");
   if (c.graph_prior == DIBS_PRIOR_EDGEWISE && c.reserved_i[0] > 1)
     return fail("batched engine (n_problems > 1): the edge-wise graph prior is not supported (the table-reading tail kernel has no edge-wise "
                 "form, and per-problem tables are not built)");
-  if (!c.joint && c.likelihood != DIBS_LIK_BGE)
-    return fail("MarginalDiBS needs a marginal likelihood (BGe)");
+  if (c.likelihood == DIBS_LIK_BDEU) {
+    // BDeu on discrete data (include/dibs_hip.h, BDEU): MarginalDiBS, score-function estimator, float32 engine
+    if (c.joint) return fail("BDeu: joint = 1 is not supported (a marginal likelihood: MarginalDiBS only)");
+    if (c.grad_estimator_z == DIBS_EST_REPARAM)
+      return fail("BDeu: the reparam estimator is not supported (a count-based score has no soft-graph form; score-function estimator only)");
+    if (c.n_observations < 1 || c.n_observations > BDEU_MAX_N)
+      return fail("BDeu: n_observations = " + std::to_string(c.n_observations) + " but must be in [1, " + std::to_string(BDEU_MAX_N) +
+                  "] (the grouping table of one wave must fit a block's LDS)");
+  }
+  if (!c.joint && !lik_marginal(c.likelihood))
+    return fail("MarginalDiBS needs a marginal likelihood (BGe, BDeu)");
   if (c.joint && c.likelihood == DIBS_LIK_BGE)
     return fail("JointDiBS + BGe is not constructible (BGe has no parameters; linearGaussian.py:53-54)");
   if (c.likelihood == DIBS_LIK_BGE && c.grad_estimator_z == DIBS_EST_REPARAM) {
@@ -367,7 +389,7 @@ extern "C" int dibs_engine_create(const dibs_config* cfg, void* stream, dibs_eng
     if (c.n_vars <= 128 && bge_soft_waves(c.n_vars, false) < 1)
       return fail("BGe + reparam estimator: n_vars too large for the device kernel");
   }
-  if (c.likelihood == DIBS_LIK_BGE && c.grad_estimator_z == DIBS_EST_SCORE &&
+  if (lik_marginal(c.likelihood) && c.grad_estimator_z == DIBS_EST_SCORE &&
       bge_sample_lds_bytes(c.n_vars, c.n_grad_mc_samples, (c.n_vars + 63) / 64) > LDS_LIMIT - 2048)
     return fail("BGe: n_grad_mc_samples too large (the parent sets of one node's samples are staged in LDS)");
   if (c.likelihood == DIBS_LIK_DENSENN) {
@@ -386,7 +408,7 @@ extern "C" int dibs_engine_create(const dibs_config* cfg, void* stream, dibs_eng
     if ((size_t)2 * 4 * c.n_particles * 4 + 4096 > LDS_LIMIT) return fail("n_particles too large (kernel rows must fit in LDS)");
     // k_particle_grad keeps a particle's score-space gradient, its Z and (score estimator) the per-sample weights in LDS; beyond that
     // size W goes through global memory (k_backproject_big) and only the per-sample weights have to fit
-    const bool score_lik = c.likelihood == DIBS_LIK_BGE && c.grad_estimator_z == DIBS_EST_SCORE;
+    const bool score_lik = lik_marginal(c.likelihood) && c.grad_estimator_z == DIBS_EST_SCORE;
     if (tail_lds_bytes(c.n_vars, 0, c.n_grad_mc_samples, (c.n_vars + 63) / 64, score_lik, 0) > LDS_LIMIT - 2048 ||
         backproject_big_lds(c.n_vars) > LDS_LIMIT - 2048)
       return fail("n_grad_mc_samples (or n_vars) too large: a particle's sample weights do not fit in LDS");
@@ -426,6 +448,7 @@ extern "C" int dibs_engine_destroy(dibs_engine* e) {
     if (p) hipFree(p);
   joint_free(&e->jw);
   delete e->f64;
+  delete e->bdeu;
   dibs_engine_comm_destroy(e);
   if (e->stream2) hipStreamDestroy(e->stream2);
   if (e->ev_fork) hipEventDestroy(e->ev_fork);

@@ -162,8 +162,104 @@ static int bge_prepare(BgeStats* st, const dibs_config& cfg, int d, int N, const
   return 0;
 }
 
+// ---- BDeu: arities, packed data, the launch (include/dibs_hip.h, BDEU; bdeu_score.h) --------------------------------------------------------
+extern "C" int dibs_engine_set_arities(dibs_engine* e, const int32_t* arities) {
+  if (!e || !arities) return fail("null argument");
+  if (!e->bdeu) return fail("dibs_engine_set_arities: not a BDeu engine (dibs_config.likelihood = DIBS_LIK_BDEU)");
+  const int d = e->d;
+  for (int i = 0; i < d; ++i)
+    if (arities[i] < BDEU_MIN_ARITY || arities[i] > BDEU_MAX_ARITY)
+      return fail("BDeu: arity " + std::to_string(arities[i]) + " of variable " + std::to_string(i) + " is outside the supported range [" +
+                  std::to_string(BDEU_MIN_ARITY) + ", " + std::to_string(BDEU_MAX_ARITY) + "]");
+  std::vector<BdeuField> f((size_t)d);
+  const int KW = bdeu_layout(arities, d, f.data());
+  if (KW > BDEU_MAX_KW)
+    return fail("BDeu: the bit fields of a packed row need " + std::to_string(KW) + " 64-bit words, more than " + std::to_string(BDEU_MAX_KW) +
+                " (512 bits: e.g. 256 variables of arity <= 4 or 128 of arity <= 16)");
+  HIP_OK(hipSetDevice(e->cfg.device_id));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  BdeuState& b = *e->bdeu;
+  e->has_data = false;  // (data packed under another layout is gone)
+  e->score_cache.valid = false;
+  b.train.release();
+  b.ho.release();
+  b.arities.assign(arities, arities + d);
+  b.fields = f;
+  b.KW = KW;
+  std::vector<double> lr((size_t)d);
+  for (int i = 0; i < d; ++i) lr[i] = log((double)arities[i]);
+  if (!b.d_fields) HIP_OK(dalloc(&b.d_fields, (size_t)d));
+  if (!b.d_log_arity) HIP_OK(dalloc(&b.d_log_arity, (size_t)d));
+  HIP_OK(hipMemcpy(b.d_fields, f.data(), (size_t)d * sizeof(BdeuField), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(b.d_log_arity, lr.data(), (size_t)d * 8, hipMemcpyHostToDevice));
+  return 0;
+}
+
+// checks every code (integral, 0 <= x < r_i), packs the rows and the per-node used-row bits, uploads them
+static int bdeu_prepare(dibs_engine* e, BdeuData* out, const char* what, const float* x, const int32_t* mask, int N) {
+  const BdeuState& b = *e->bdeu;
+  if (b.arities.empty()) return fail(std::string("BDeu: ") + what + ": dibs_engine_set_arities has not been called");
+  BdeuPlan pl;
+  if (N < 1 || !bdeu_plan(N, b.KW, &pl))
+    return fail(std::string("BDeu: ") + what + ": " + std::to_string(N) + " observations, but the kernel supports 1 .. " + std::to_string(BDEU_MAX_N) +
+                " (the grouping table of one wave must fit a block's LDS)");
+  const int d = e->d, KW = b.KW, NW = (N + 63) / 64;
+  std::vector<uint64_t> rows((size_t)KW * N, 0ull), used((size_t)d * NW, 0ull);
+  std::vector<int32_t> nused((size_t)d, 0), codes((size_t)d);
+  for (int n = 0; n < N; ++n) {
+    for (int i = 0; i < d; ++i) {
+      const float v = x[(size_t)n * d + i];
+      if (!(v >= 0.0f && v < (float)b.arities[i] && v == floorf(v))) {
+        char buf[64];
+        snprintf(buf, sizeof buf, "%g", (double)v);
+        return fail(std::string("BDeu: ") + what + ": x[" + std::to_string(n) + ", " + std::to_string(i) + "] = " + buf +
+                    " is not a category code of variable " + std::to_string(i) + " (integers 0 .. " + std::to_string(b.arities[i] - 1) + ")");
+      }
+      codes[i] = (int32_t)v;
+      if (!(mask && mask[(size_t)n * d + i] != 0)) {
+        used[(size_t)i * NW + (n >> 6)] |= 1ull << (n & 63);
+        ++nused[i];
+      }
+    }
+    bdeu_pack_row(codes.data(), d, b.fields.data(), rows.data(), (size_t)N, (size_t)n);
+  }
+  out->release();
+  HIP_OK(dalloc(&out->rows, rows.size()));
+  HIP_OK(dalloc(&out->used, used.size()));
+  HIP_OK(dalloc(&out->nused, nused.size()));
+  HIP_OK(hipMemcpy(out->rows, rows.data(), rows.size() * 8, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(out->used, used.data(), used.size() * 8, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(out->nused, nused.data(), nused.size() * 4, hipMemcpyHostToDevice));
+  out->N = N;
+  out->NW = NW;
+  return 0;
+}
+
+int bdeu_launch(dibs_engine* e, hipStream_t st, const BdeuData& data, const uint64_t* masks, double* node_scores, long long nprob, int S) {
+  const BdeuState& b = *e->bdeu;
+  BdeuArgs a{};
+  a.rows = data.rows;
+  a.used = data.used;
+  a.nused = data.nused;
+  a.fields = b.d_fields;
+  a.log_arity = b.d_log_arity;
+  a.masks = masks;
+  a.node_scores = node_scores;
+  a.log_ess = b.log_ess;
+  a.nprob = nprob;
+  a.N = data.N;
+  a.KW = b.KW;
+  a.NW = data.NW;
+  a.d = e->d;
+  a.S = S;
+  a.W = e->W;
+  if (!data.rows || bdeu_launch_nodes(st, a)) return fail("BDeu: no data, or no LDS plan for its size");
+  return 0;
+}
+
 extern "C" int dibs_engine_set_data(dibs_engine* e, const float* x, const int32_t* interv_mask, const float* bge_mean_obs) {
   if (!e || !x) return fail("null argument");
+  if (e->bdeu && e->bdeu->arities.empty()) return fail("BDeu: dibs_engine_set_data: dibs_engine_set_arities has not been called");
   if (e->B > 1 && !e->chains) return fail("batched engine: use dibs_engine_set_data_problem");
   if (e->chains && !e->cdata.set.empty())
     return fail("chains engine (n_chains > 1): dibs_engine_set_data after dibs_engine_set_data_problem is not supported (the chains of this engine "
@@ -194,6 +290,8 @@ extern "C" int dibs_engine_set_data(dibs_engine* e, const float* x, const int32_
     e->has_mean_obs = bge_mean_obs != nullptr;
     if (bge_mean_obs) e->mean_obs.assign(bge_mean_obs, bge_mean_obs + e->d);
     if (bge_prepare(&e->bge, e->cfg, e->d, e->N, x, interv_mask, bge_mean_obs)) return 1;
+  } else if (e->cfg.likelihood == DIBS_LIK_BDEU) {
+    if (bdeu_prepare(e, &e->bdeu->train, "dibs_engine_set_data", x, interv_mask, e->N)) return 1;
   } else {
     if (joint_set_data(&e->jw, x, interv_mask, e->N, e->d)) return fail("joint_set_data failed");
     if (e->cfg.likelihood == DIBS_LIK_LINGAUSS && !joint_lin_fast_path(e->d, e->N, e->tune.lin_gram) && joint_lin_set_gram(&e->jw, x, interv_mask, e->N, e->d))
@@ -363,6 +461,28 @@ extern "C" int dibs_score_graphs(dibs_engine* e, const int32_t* g, const float* 
                         KmatFuse{nullptr, nullptr, 0, 0, 0, 0.f, 0.f, nullptr, 0u});
       bge_launch_chol(e->stream, d_ns.p, bp, sq, d, S, nullptr);
       bge_launch_sum_nodes(e->stream, d_ns.p, d_out.p + q0, d, S);
+      HIP_OK(hipStreamSynchronize(e->stream));
+    }
+  } else if (c.likelihood == DIBS_LIK_BDEU) {
+    if (e->bdeu->arities.empty()) return fail("BDeu: dibs_score_graphs: dibs_engine_set_arities has not been called");
+    if (!cached) {
+      if (bdeu_prepare(e, &e->bdeu->ho, "dibs_score_graphs", x_ho, mask_ho, n_ho)) return 1;
+      sc.remember(x_ho, mask_ho, n_x);
+    }
+    // chunks of n_grad_mc_samples graphs through the engine's own parent-set and node-score buffers ([1 .. Mloc][d][S][W] / [..][d][S]: a
+    // chunk of S' <= S graphs fills the first d S' entries as [d][S']): the last chunk's doubles stay readable (include/dibs_hip.h, BDEU)
+    const int W = e->W, CH = e->S;
+    std::vector<uint64_t> hm((size_t)d * CH * W);
+    for (int q0 = 0; q0 < n; q0 += CH) {
+      const int S = n - q0 < CH ? n - q0 : CH;
+      std::fill(hm.begin(), hm.end(), 0ull);
+      for (int s = 0; s < S; ++s)
+        for (int i = 0; i < d; ++i)
+          for (int j = 0; j < d; ++j)
+            if (i != j && g[(size_t)(q0 + s) * dd + (size_t)i * d + j] != 0) hm[((size_t)j * S + s) * W + (i >> 6)] |= 1ull << (i & 63);
+      HIP_OK(hipMemcpy(e->masks, hm.data(), (size_t)d * S * W * 8, hipMemcpyHostToDevice));
+      if (bdeu_launch(e, e->stream, e->bdeu->ho, e->masks, e->node_scores, (long long)d * S, S)) return 1;
+      bge_launch_sum_nodes(e->stream, e->node_scores, d_out.p + q0, d, S);
       HIP_OK(hipStreamSynchronize(e->stream));
     }
   } else if (c.likelihood == DIBS_LIK_LINGAUSS || c.likelihood == DIBS_LIK_DENSENN) {

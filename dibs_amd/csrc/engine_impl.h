@@ -57,6 +57,41 @@ struct BgeStats {
   BgeParams params() const { return BgeParams{Rp, Qp, gam, Nj, ldR, alpha_lambd, n_mats}; }
 };
 
+// BDeu (DIBS_LIK_BDEU; kernels_bdeu.h, bdeu_score.h): one data set as k_bdeu_nodes reads it -- packed rows, per-node used-row bits and
+// counts.  Owns its device buffers.
+struct BdeuData {
+  uint64_t *rows = nullptr, *used = nullptr;  // [KW][N], [d][NW]
+  int32_t* nused = nullptr;                   // [d]
+  int N = 0, NW = 0;
+  void release() {
+    void* ptrs[] = {rows, used, nused};
+    for (void* p_ : ptrs)
+      if (p_) hipFree(p_);
+    rows = used = nullptr;
+    nused = nullptr;
+    N = NW = 0;
+  }
+  ~BdeuData() { release(); }
+  BdeuData() = default;
+  BdeuData(const BdeuData&) = delete;
+  BdeuData& operator=(const BdeuData&) = delete;
+};
+// ... and what dibs_engine_set_arities fixes: the arities, the field layout of a packed row and log r_i
+struct BdeuState {
+  std::vector<int32_t> arities;
+  std::vector<BdeuField> fields;
+  int KW = 0;
+  BdeuField* d_fields = nullptr;
+  double* d_log_arity = nullptr;
+  double log_ess = 0.0;
+  BdeuData train, ho;  // the engine's data (dibs_engine_set_data); the last held-out set dibs_score_graphs scored against
+  ~BdeuState() {
+    if (d_fields) hipFree(d_fields);
+    if (d_log_arity) hipFree(d_log_arity);
+  }
+};
+inline bool lik_marginal(int likelihood) { return likelihood == DIBS_LIK_BGE || likelihood == DIBS_LIK_BDEU; }
+
 // the float64 engine's device state (dibs_config.reserved_i[1] = 64; kernels_f64.h): loop carry, per-step buffers and the BGe statistics in
 // double.  The parent sets and node scores go to the f32 engine's PARENT_MASKS / NODE_SCORES buffers (same layouts).
 struct F64State {
@@ -131,6 +166,7 @@ struct dibs_engine {
   float* x;
   int32_t* mask;
   BgeStats bge;
+  BdeuState* bdeu = nullptr;  // DIBS_LIK_BDEU (engine_alloc); `bge` then holds zero tables for the shared sampling launch, which are never scored
   float* soft_ds;  // [Mloc, S, d, d]  BGe reparam estimator: per-sample score-space gradients
   float* soft_tri = nullptr;  // ... beyond 128 variables: the waves' packed triangles (factor | inverse columns) in global scratch
   int soft_blocks = 0;        //     of this many persistent blocks (kernels_bge_soft.h, GLOB)
@@ -392,6 +428,8 @@ bool chains_hp_differ(const dibs_engine* e);  // (engine.hip: some chain's host 
 // selection that writes h / h_theta of every run's table row and bw [C][2] (rule: dibs_config.reserved_i[3]) ----
 void bandwidth_launch_sqdist(hipStream_t st, bool tiled, const float* x, size_t len, float* out, int C, int M, size_t lds_direct);
 void bandwidth_launch_select(hipStream_t st, const float* sqd_z, const float* sqd_t, int rule, int C, int M, ProblemHP* hp, float* bw);
+// ---- engine_data.hip: BDeu -- k_bdeu_nodes over `nprob` parent sets of `masks` against one packed data set ----
+int bdeu_launch(dibs_engine* e, hipStream_t st, const BdeuData& data, const uint64_t* masks, double* node_scores, long long nprob, int S);
 // ---- engine_f64.hip ----
 int f64_alloc(dibs_engine* e);
 int f64_init_particles(dibs_engine* e, Key2 isub);

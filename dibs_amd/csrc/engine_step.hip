@@ -509,7 +509,10 @@ int step_local(dibs_engine* e, int t, const RowTarget& rt, const StepKeys* xk, i
       bge_launch_sample(true, e->stream, e->thr, e->masks, e->node_scores, bp, carry_lik, e->m0, Mg, e->Mloc, e->d, e->S, e->W, L,
                         e->bq, kf);
     }
-    {
+    if (c.likelihood == DIBS_LIK_BDEU) {  // the second producer of the node scores: counts of the sampled parent sets' configurations
+      KTimer tm(e, DIBS_K_BGE_BIG);
+      if (bdeu_launch(e, e->stream, e->bdeu->train, e->masks, e->node_scores, (long long)e->Mloc * e->d * e->S, e->S)) return 1;
+    } else {
       KTimer tm(e, DIBS_K_BGE_BIG);
       bge_launch_chol(e->stream, e->node_scores, bp, e->bq, e->d, e->S, e->profiling ? e->counters : nullptr);
     }

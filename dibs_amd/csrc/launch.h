@@ -5,6 +5,7 @@
 #include "common.h"
 #include "kernels_kmat.h"
 #include "kernels_bge.h"
+#include "kernels_bdeu.h"
 #include "tuning.h"
 
 // kernels that may need more than the default 64 KiB of dynamic LDS: raises hipFuncAttributeMaxDynamicSharedMemorySize once per
@@ -26,6 +27,9 @@ void bge_launch_sample_batch(hipStream_t stream, const uint32_t* thr, uint64_t* 
                              int Mloc, int d, int S, int W, int layout, const BgeQueues& qs);
 void bge_launch_chol_batch(hipStream_t stream, double* node_scores, const BgeParams& bp, const BgeQueues& qs, int d, int S);
 void bge_launch_sum_nodes(hipStream_t stream, const double* node_scores, float* out, int d, int S);
+
+// ---- tu_bdeu.hip: BDeu node scores of the parent sets in `masks` (kernels_bdeu.h); the LDS plan's fields of `a` are filled in ---------
+int bdeu_launch_nodes(hipStream_t stream, BdeuArgs a);
 
 // ---- tu_acyc.hip -------------------------------------------------------------------------------------
 struct AcycLaunch {

@@ -59,7 +59,7 @@ enum class JoinKind {
 
 struct StepPlan {
   bool do_lik, do_prior;
-  bool score_lik;  // the likelihood part is BGe's score estimator (k_bge_sample, k_bge_chol; W_lik is formed inside k_particle_grad)
+  bool score_lik;  // the likelihood part is BGe's or BDeu's score estimator (k_bge_sample, k_bge_chol / k_bdeu_nodes; W_lik is formed inside k_particle_grad)
   KmatPlace place;
   ForkKind fork;
   JoinKind join;
@@ -76,7 +76,9 @@ inline bool kmat_tiled_on(int kmat_ns_max, int M, int kmat_tiled_min) { return k
 static inline StepPlan plan_step(const StepFacts& f) {
   StepPlan p{(f.terms & TERMS_LIK) != 0, (f.terms & TERMS_PRIOR) != 0, false, KmatPlace::PhaseB, ForkKind::None, JoinKind::None, 0, 0, 0};
   const bool single_rank = f.Mloc == f.M;
-  p.score_lik = p.do_lik && f.likelihood == DIBS_LIK_BGE && f.estimator == DIBS_EST_SCORE;  // (the estimator is SCORE or REPARAM: dibs_engine_create)
+  // (BDeu: the same schedule with k_bdeu_nodes in the place of k_bge_chol; it admits the score estimator only.  The estimator is SCORE or
+  //  REPARAM: dibs_engine_create)
+  p.score_lik = p.do_lik && (f.likelihood == DIBS_LIK_BGE || f.likelihood == DIBS_LIK_BDEU) && f.estimator == DIBS_EST_SCORE;
 
   // ---- the second stream ----
   // The acyclicity chain runs on the second stream beside the likelihood chain whenever a step has both.

@@ -62,6 +62,14 @@ class Engine:
             raise ValueError(f"edge_probs must have shape ({self.d}, {self.d}), got {p.shape}")
         _lib.check(self.lib.dibs_engine_set_edge_prior(self._h, _ptr(p)))
 
+    def set_arities(self, arities):
+        """The values per variable of a BDeu engine (include/dibs_hip.h, dibs_engine_set_arities): int ``[d]``, each 2 .. 16.  Before
+        ``set_data`` and before scoring."""
+        a = np.ascontiguousarray(arities, np.int32)
+        if a.shape != (self.d,):
+            raise ValueError(f"arities must have shape ({self.d},), got {a.shape}")
+        _lib.check(self.lib.dibs_engine_set_arities(self._h, _ptr(a)))
+
     # batched engine (n_problems > 1): per-problem data, particles and loop-carry keys
     def set_data_problem(self, p, x, interv_mask=None, bge_mean_obs=None):
         x = np.ascontiguousarray(x, np.float32)

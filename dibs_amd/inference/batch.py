@@ -15,6 +15,9 @@ def _batchable(models, keys, who):
     def rule(i, m):
         if m.grad_estimator_z != "score":
             raise ValueError(f"{who}: only the score-function estimator is batched (grad_estimator_z='score')")
+        if getattr(m.likelihood_model, "_dibs_likelihood", None) == "bdeu":
+            raise ValueError(f"{who}: model {i} has a BDeu likelihood (discrete data), which the batched engine does not support: it runs "
+                             "BGe only (use sample() per problem)")
     not_marginal = lambda i, m: "every model must be a MarginalDiBS (joint models are not batched)"
     models, keys = _multirun.check_runs(models, keys, who, MarginalDiBS, not_marginal, rule, "not batched")
     _multirun._refuse_edgewise(models, who, "the batched engine")

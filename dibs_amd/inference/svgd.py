@@ -56,10 +56,18 @@ class _SVGDBase(DiBS):
                                       "UniformDAGDistributionRejection, EdgePriorDAGDistribution (arbitrary callables cannot be lowered "
                                       "to the device)")
         lik = getattr(likelihood_model, "_dibs_likelihood", None)
-        allowed = ("lingauss", "densenn") if self._joint else ("bge",)
+        allowed = ("lingauss", "densenn") if self._joint else ("bge", "bdeu")
         if lik not in allowed:
             raise NotImplementedError(f"likelihood_model must be one of {allowed} for {type(self).__name__}; "
                                       "arbitrary callables cannot be lowered to the device")
+        if lik == "bdeu":
+            # discrete data: category codes, checked here column by column (the engine checks them again, entry by entry)
+            likelihood_model.check_data(x)
+            if grad_estimator_z == "reparam":
+                raise ValueError("BDeu: grad_estimator_z='reparam' is not supported (a count-based score has no soft-graph form); use 'score'")
+            if precision == "float64":
+                raise ValueError("BDeu: precision='float64' is not supported (the float64 engine runs BGe only; the BDeu node scores are "
+                                 "double on the float32 engine)")
         self.kernel = kernel(**kernel_param)
         if self._joint:
             if not isinstance(self.kernel, JointAdditiveFrobeniusSEKernel):
@@ -94,6 +102,8 @@ class _SVGDBase(DiBS):
 
     def _new_engine(self, n_particles, n_dim, stream=None, **kw):
         eng = Engine(self._make_config(n_particles, n_dim, **kw), stream=stream)
+        if self.likelihood_model._dibs_likelihood == "bdeu":
+            eng.set_arities(self.likelihood_model.arities)
         eng.set_data(self.x if self._x_engine is None else self._x_engine, self.interv_mask if self.interv_mask.any() else None,
                      getattr(self.likelihood_model, "mean_obs", None))
         if self.graph_model._dibs_prior == "edgewise":
@@ -204,7 +214,8 @@ class _SVGDBase(DiBS):
 
 
 class MarginalDiBS(_SVGDBase):
-    """SVGD inference of p(G | D) with a closed-form marginal likelihood (BGe)."""
+    """SVGD inference of p(G | D) with a closed-form marginal likelihood: BGe (linear-Gaussian data) or BDeu (discrete data, ``models.BDeu``:
+    ``x`` holds category codes; score-function estimator, float32 engine)."""
     _joint = False
 
     def __init__(self, *, x, graph_model, likelihood_model, interv_mask=None, kernel=AdditiveFrobeniusSEKernel,

@@ -6,7 +6,8 @@ from typing import Any, NamedTuple
 import numpy as np
 
 from . import random
-from .models import (BGe, DenseNonlinearGaussian, ErdosReniDAGDistribution, LinearGaussian, ScaleFreeDAGDistribution,
+from .graph_utils import topological_order
+from .models import (BDeu, BGe, DenseNonlinearGaussian, ErdosReniDAGDistribution, LinearGaussian, ScaleFreeDAGDistribution,
                      UniformDAGDistributionRejection)
 
 
@@ -87,3 +88,54 @@ def make_nonlinear_gaussian_model(*, key, n_vars=20, graph_prior_str="sf", obs_n
                                     generative_model=DenseNonlinearGaussian(**kw), n_observations=n_observations,
                                     n_ho_observations=n_ho_observations)
     return data, graph_model, DenseNonlinearGaussian(**kw)
+
+
+def _sample_discrete(rng, g, order, cpts, arities, n, interv=None):
+    """ancestral sampling of n rows of category codes from per-node conditional probability tables; ``interv`` = {node: clamp value}"""
+    interv = interv or {}
+    d = g.shape[0]
+    x = np.zeros((n, d), np.int64)
+    for j in order:
+        if j in interv:
+            x[:, j] = interv[j]
+            continue
+        pa = np.where(g[:, j])[0]
+        cfg = np.zeros(n, np.int64)   # mixed-radix index of the parent configuration
+        for i in pa:
+            cfg = cfg * arities[i] + x[:, i]
+        cdf = np.cumsum(cpts[j][cfg], axis=1)
+        x[:, j] = np.minimum((rng.random(n)[:, None] > cdf).sum(axis=1), arities[j] - 1)
+    return x.astype(np.float32)
+
+
+def make_discrete_model(*, key, n_vars, arities=3, n_observations=100, n_ho_observations=100, graph_prior_str="er", edges_per_node=2,
+                        n_intervention_sets=0, dirichlet_alpha=0.5, equivalent_sample_size=1.0):
+    """A ground-truth discrete Bayes net and data from it, for ``MarginalDiBS`` with the ``BDeu`` likelihood: a DAG from the graph prior,
+    per node and parent configuration one conditional probability table row drawn from Dirichlet(``dirichlet_alpha``), ancestral sampling
+    on the host.  ``data.x`` / ``data.x_ho`` hold category codes (float32); ``data.theta`` is the list of tables (``[q_j, r_j]`` per
+    node); ``data.x_interv`` a list of ``(interv, x)`` as the other factories build it, ``interv = {node: category}`` clamping one node
+    per set.  Host numpy: deterministic per key."""
+    key = random.as_key(key)
+    graph_model = make_graph_model(n_vars=n_vars, graph_prior_str=graph_prior_str, edges_per_node=edges_per_node)
+    lik = BDeu(n_vars=n_vars, arities=arities, equivalent_sample_size=equivalent_sample_size)
+    r = lik.arities.astype(np.int64)
+    passed_key = key.copy()
+    key, subk = random.split(key)
+    g = np.asarray(graph_model.sample_G(subk))
+    key, subk = random.split(key)
+    rng = np.random.default_rng([int(v) for v in np.asarray(subk, np.uint32)])
+    order = topological_order(g)
+    cpts = []
+    for j in range(n_vars):
+        q = int(np.prod(r[np.where(g[:, j])[0]]))
+        cpts.append(rng.dirichlet(np.full(r[j], float(dirichlet_alpha)), size=q))
+    x = _sample_discrete(rng, g, order, cpts, r, n_observations)
+    x_ho = _sample_discrete(rng, g, order, cpts, r, n_ho_observations)
+    x_interv = []
+    for _ in range(n_intervention_sets):
+        node = int(rng.integers(n_vars))
+        interv = {node: int(rng.integers(r[node]))}
+        x_interv.append((interv, _sample_discrete(rng, g, order, cpts, r, n_observations, interv)))
+    data = Data(passed_key=passed_key, n_vars=n_vars, n_observations=n_observations, n_ho_observations=n_ho_observations,
+                g=g, theta=cpts, x=x, x_ho=x_ho, x_interv=x_interv)
+    return data, graph_model, lik

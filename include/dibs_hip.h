@@ -24,7 +24,7 @@ extern "C" {
 #define DIBS_ABI_VERSION 2
 #define DIBS_MAX_HIDDEN_LAYERS 8
 
-enum { DIBS_LIK_BGE = 0, DIBS_LIK_LINGAUSS = 1, DIBS_LIK_DENSENN = 2 };
+enum { DIBS_LIK_BGE = 0, DIBS_LIK_LINGAUSS = 1, DIBS_LIK_DENSENN = 2, DIBS_LIK_BDEU = 3 /* discrete data: see BDEU */ };
 enum { DIBS_PRIOR_ER = 0, DIBS_PRIOR_SF = 1, DIBS_PRIOR_UNIFORM = 2, DIBS_PRIOR_EDGEWISE = 3 /* see dibs_engine_set_edge_prior */ };
 enum { DIBS_EST_SCORE = 0, DIBS_EST_REPARAM = 1 };
 enum { DIBS_OPT_GD = 0, DIBS_OPT_RMSPROP = 1 };
@@ -82,7 +82,7 @@ typedef struct dibs_config {
   double lin_min_edge;
   double nn_obs_noise;      /* nonlinearGaussian.py:105 */
   double nn_sig_param;
-  double reserved_d[6];
+  double reserved_d[6];     /* [0] DIBS_LIK_BDEU: the equivalent sample size; <= 0 means 1.0 (see BDEU) */
 } dibs_config;
 
 typedef struct dibs_engine dibs_engine;
@@ -391,6 +391,31 @@ int dibs_engine_set_edge_prior(dibs_engine* e, const double* edge_probs);
  * Limits, each an error of dibs_engine_create that starts "median bandwidth: ": n_particles (per run) >= 256 (the GEMM form of the SVGD
  * transform has no table-reading form and the selection is one block per run: the follow-up), n_particles < 2, n_ranks > 1, the float64
  * engine, bit 1 on a marginal model, a rule outside 0 .. 3; dibs_engine_kmat_values on such an engine fails the same way. */
+
+/* BDEU: MarginalDiBS on DISCRETE data (no reference counterpart as a class; the score is the Bayesian-Dirichlet equivalent uniform
+ * marginal likelihood of Heckerman, Geiger & Chickering 1995).  dibs_config.likelihood = DIBS_LIK_BDEU, dibs_config.reserved_d[0] = the
+ * equivalent sample size eta (<= 0: 1.0).  x holds category codes as floats: variable i has arity r_i and takes the values 0 .. r_i - 1.
+ *   node j uses the rows n with interv_mask[n, j] == 0 (a parent's value is used in every such row);  pa = {i : g[i, j] = 1}
+ *   log a = log eta - sum_{i in pa} log r_i,   log a' = log a - log r_j
+ *   rise(log alpha, n) = 0 for n = 0,  log alpha + sum_{i=1}^{n-1} log(exp(log alpha) + i) for n >= 1   (= lgamma(alpha + n) - lgamma(alpha))
+ *   score_j = sum over the parent configurations c that occur in the used rows:  - rise(log a, N_c) + sum_k rise(log a', N_ck)
+ *   log p(D | G) = sum_j score_j;  a node without used rows scores 0.
+ * All arithmetic is double, counts are integers, and the value does not depend on the order in which threads arrive.
+ * The step is the BGe score estimator's with one kernel exchanged: the same sampling launch (the same Threefry streams, so the same
+ * graphs for a key), k_bdeu_nodes in the place of the factorisation, then everything that consumes DIBS_BUF_NODE_SCORES.  Its time is
+ * reported under DIBS_K_BGE_BIG.  DIBS_BUF_NODE_SCORES / DIBS_BUF_PARENT_MASKS read back as for BGe.
+ *   dibs_engine_set_arities(e, arities)   arities: i32 [d].  Required before dibs_engine_set_data and before dibs_score_graphs on a BDeu
+ *       engine (either call without it is an error, never a default); an error on an engine that is not BDeu.  Fails for an arity outside
+ *       2 .. 16 and when the bit fields of a packed row (ceil(log2 r_i) bits per variable, no field straddling a 64-bit word) need more
+ *       than 512 bits -- e.g. 256 variables of arity <= 4 or 128 of arity <= 16 fit.  Calling it again discards the engine's data.
+ * dibs_engine_set_data / dibs_score_graphs keep their signatures; they check every entry of x / x_ho to be integral and in [0, r_i) and
+ * fail with the row and column of the first that is not.  n_observations / n_ho may be at most 4096 (one wave's grouping table must fit a
+ * block's LDS; the message states the limit).  On a BDeu engine dibs_score_graphs works in chunks of n_grad_mc_samples graphs and leaves
+ * the last chunk's parent sets and per-node scores (double) in DIBS_BUF_PARENT_MASKS / DIBS_BUF_NODE_SCORES, laid out [d][S'][W] / [d][S']
+ * with S' the chunk's graph count, at the start of the buffers: `out` is float, the sum over the nodes of those doubles is not rounded.
+ * dibs_engine_create refuses, each with a message that starts "BDeu: ": joint = 1, the reparam estimator (a count-based score has no
+ * soft-graph form), n_observations > 4096.  The float64, batched and chains engines refuse the likelihood as they refuse any but their own. */
+int dibs_engine_set_arities(dibs_engine* e, const int32_t* arities);
 
 /* debugging / parity: copy a device buffer to the host (nbytes must match); theta size query */
 int dibs_engine_read_buffer(dibs_engine* e, int32_t which, void* host, int64_t nbytes);
