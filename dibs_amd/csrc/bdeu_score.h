@@ -94,6 +94,12 @@ BDEU_HD inline uint64_t bdeu_mix(uint64_t h, uint64_t v) {
   h = (h ^ v) * 0x9E3779B97F4A7C15ull;
   return h ^ (h >> 29);
 }
+// first slot of a probe sequence in a table of T slots (a power of two, 64 .. 8192): the TOP log2 T bits of one more odd multiple of the
+// mixed hash.  A product carries every bit upwards only, so its top bits depend on all 64 bits of every key word; a window lower down
+// (bits 32 .. 44 of h were used once) never sees a field above it, and parents that sit late in a word all landed in a few slots.  The
+// second multiplier is there because the low half of bdeu_mix's is close to 2^31: the top bits of h alone alternate between two runs for
+// consecutive codes of a field at bit 32 (tests/tools/bdeu_score_check.cpp, check_hash).
+BDEU_HD inline uint32_t bdeu_slot(uint64_t h, uint32_t T) { return (uint32_t)((h * 0xD6E8FEB86659FD93ull) >> (64 - __builtin_ctz(T))); }
 
 // LDS plan of k_bdeu_nodes for N observations of KW words.  Per wave: key mask [8] u64 | rise prefix table [N] f64 | slots rep, minrow,
 // cnt [T] u32 each | slot of every row [N] u32, T = the power of two >= 2 N (load factor <= 1/2).  Per block: the packed rows, when they

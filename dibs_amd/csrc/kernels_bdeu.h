@@ -77,7 +77,7 @@ __device__ __forceinline__ double bdeu_pass(const uint64_t* __restrict__ rows, c
         const uint64_t kw = km[w];
         if (kw) h = bdeu_mix(h, rows[(size_t)w * N + n] & kw);
       }
-      uint32_t slot = (uint32_t)(h >> 32) & (T - 1u);
+      uint32_t slot = bdeu_slot(h, T);
       bool found = false;
       for (uint32_t probe = 0; probe < T; ++probe) {  // (load factor <= 1/2: an empty slot ends every probe sequence)
         uint32_t r = atomicCAS(&rep[slot], BDEU_EMPTY, (uint32_t)n);

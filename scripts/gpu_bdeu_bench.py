@@ -8,6 +8,11 @@ costs the paths that do not use it, and what the posterior looks like, on one MI
                 Gaussian data.  Alternating runs, medians and ranges.  No gate: nobody had measured this kernel.  Then one run per side
                 with per-kernel timing (dibs_engine_set_profiling(1): every kernel alone on the GPU): microseconds per step and kernel
                 family; k_bdeu_nodes is reported in k_bge_chol's slot, "bge_big".
+  high_bits     one scoring call whose parents' fields are the top bits of the key word: d = 30, arity 4, N = 1 024, columns 24 .. 29 the
+                base-4 digits of a permutation of the rows (1 024 configurations in bits 48 .. 59); 128 graphs in which every node's
+                parents are columns 24 .. 29, beside the same call with parents 0 .. 5 (random columns, low bits).  Milliseconds per
+                dibs_score_graphs call (3 840 problems; host mask building and the copy of the result included), median of seven.
+                A record: what the table's slot function costs where the old one clustered.
   single_path   with --parent-root (a checkout of the parent commit with its library built): bench.py --dump-outputs of the headline
                 config and config 3 from both trees (np.array_equal per array), and ms_per_step of five alternating plain bench.py runs
                 each.  Gate: this tree's median inside the parent's [min, max] widened by (max - min) on either side.
@@ -76,6 +81,36 @@ def one(lik, name, steps, warmup, timers):
     return out
 
 
+def high_bits():
+    """a child: the scoring call on top-bit parents and on low-bit parents"""
+    import numpy as np
+    from dibs_amd.inference.scoring import score_graphs
+    from dibs_amd.models import BDeu
+    d, N, n = 30, 1024, S
+    rng = np.random.default_rng(0)
+    x = rng.integers(0, 4, size=(N, d))
+    digits = rng.permutation(N)
+    for i in range(24, 30):
+        x[:, i] = digits % 4
+        digits = digits // 4
+    x = x.astype(np.float32)
+    lm = BDeu(n_vars=d, arities=4)
+    out = {}
+    for name, pa in (("parents_24_29", range(24, 30)), ("parents_0_5", range(0, 6))):
+        g = np.zeros((d, d), np.int32)
+        g[list(pa), :] = 1
+        g[np.arange(d), np.arange(d)] = 0
+        gs = np.ascontiguousarray(np.broadcast_to(g, (n, d, d)))
+        score_graphs(lm, gs, None, x)                                  # (packs the rows, builds the engine)
+        times = []
+        for _ in range(7):
+            t0 = time.perf_counter()
+            v = score_graphs(lm, gs, None, x)
+            times.append(1e3 * (time.perf_counter() - t0))
+        out[name] = dict(ms_per_call=sorted(times)[3], min_ms=min(times), max_ms=max(times), problems=d * n, score=float(v[0]))
+    return out
+
+
 def posterior(seed, steps):
     """a child: one discrete problem; E-SHD of the mixture after `steps` steps beside the empty graph's SHD"""
     import numpy as np
@@ -134,10 +169,15 @@ def main():
     ap.add_argument("--size", help=argparse.SUPPRESS)
     ap.add_argument("--posterior-seed", type=int, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--timers", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--high-bits", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.one:
         sys.path.insert(0, HERE)
         print(json.dumps(one(a.one, a.size, a.steps, a.warmup, a.timers)))
+        return 0
+    if a.high_bits:
+        sys.path.insert(0, HERE)
+        print(json.dumps(high_bits()))
         return 0
     if a.posterior_seed is not None:
         sys.path.insert(0, HERE)
@@ -168,6 +208,10 @@ def main():
         out["sizes"][name] = row
         print("cost", name, json.dumps(row), flush=True)
         save()
+
+    out["high_bits"] = dict(d=30, arity=4, N=1024, graphs=S, **_child(HERE, [os.path.abspath(__file__), "--high-bits"], 600))
+    print("high_bits", json.dumps(out["high_bits"]), flush=True)
+    save()
 
     # 2. the posterior record
     if a.posterior_out:

@@ -1,17 +1,20 @@
 """Host-side checks of the BDeu marginal likelihood on discrete data (include/dibs_hip.h, BDEU): the float64
-definition ``bdeu_log_marginal_numpy`` against an independent restatement with ``scipy.special.gammaln`` and against the properties a
-BDeu score has; the plain-C++ header the kernel shares with the host (tests/tools/bdeu_score_check.cpp); the facade's lowering and every
+definition ``bdeu_log_marginal_numpy`` against an independent restatement with the log-gamma function (``mpmath.loggamma``, 40 digits)
+and against the properties a BDeu score has; the plain-C++ header the kernel shares with the host (tests/tools/bdeu_score_check.cpp), and that the cases of
+tests/bdeu_states.py reach every launch shape its plan can pick; the facade's lowering and every
 refusal (those of dibs_engine_create come before any device call, so they run without a GPU); the discrete-data factory."""
+import fractions
+import functools
 import itertools
-import os
 import subprocess
 import tempfile
 
+import mpmath
 import numpy as np
 import pytest
-from scipy.special import gammaln
 
-from bdeu_states import CASES, GRAPHS, make_case, make_graphs
+from bdeu_states import (CASES, PLAN_TIERS, TIER_CASES, arities_of, build_score_check, graph_names, key_words, make_case, make_graphs,
+                         plan_of)
 from dibs_amd import random
 from dibs_amd._abi import LIK, make_config
 from dibs_amd._lib import DibsHipError
@@ -21,24 +24,34 @@ from dibs_amd.inference import JointDiBS, MarginalDiBS, sample_batch, sample_swe
 from dibs_amd.models import BDeu, ErdosReniDAGDistribution, bdeu_log_marginal_numpy
 from dibs_amd.target import make_discrete_model
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+@functools.lru_cache(maxsize=None)
+def _lgamma(num, den, n):
+    """lgamma(num / den + n) to 40 digits: at n = 4 096 a float64 gammaln is near 3e4, one ulp 3.6e-12, and a node of few large groups
+    is a difference of such values four orders smaller"""
+    return mpmath.loggamma(mpmath.mpf(num) / den + n)
 
 
 def restated(g, x, arities, mask, eta):
-    """BDeu as the textbooks write it: every one of the q configurations enumerated, gammaln of alpha itself"""
+    """BDeu as the textbooks write it: every one of the q configurations enumerated, the log-gamma function of alpha itself; evaluated
+    with 40 digits and rounded once"""
     x = np.asarray(x, np.int64)
     N, d = x.shape
-    total = 0.0
-    for j in range(d):
-        rows = np.ones(N, bool) if mask is None else mask[:, j] == 0
-        pa = [i for i in range(d) if i != j and g[i, j]]
-        q = int(np.prod([arities[i] for i in pa])) if pa else 1
-        a, a1 = eta / q, eta / (q * arities[j])
-        for conf in itertools.product(*[range(arities[i]) for i in pa]):
-            sel = rows & np.all(x[:, pa] == np.asarray(conf, np.int64), axis=1) if pa else rows
-            n_ck = np.bincount(x[sel, j], minlength=arities[j])
-            total += gammaln(a) - gammaln(a + n_ck.sum()) + np.sum(gammaln(a1 + n_ck) - gammaln(a1))
-    return float(total)
+    eta = fractions.Fraction(eta)
+    with mpmath.workdps(40):
+        total = mpmath.mpf(0)
+        for j in range(d):
+            rows = np.ones(N, bool) if mask is None else mask[:, j] == 0
+            pa = [i for i in range(d) if i != j and g[i, j]]
+            q = int(np.prod([arities[i] for i in pa])) if pa else 1
+            a, a1 = eta / q, eta / (q * int(arities[j]))
+            for conf in itertools.product(*[range(arities[i]) for i in pa]):
+                sel = rows & np.all(x[:, pa] == np.asarray(conf, np.int64), axis=1) if pa else rows
+                n_ck = np.bincount(x[sel, j], minlength=arities[j])
+                total += _lgamma(a.numerator, a.denominator, 0) - _lgamma(a.numerator, a.denominator, int(n_ck.sum()))
+                for v in n_ck:
+                    total += _lgamma(a1.numerator, a1.denominator, int(v)) - _lgamma(a1.numerator, a1.denominator, 0)
+        return float(total)
 
 
 def _max_q(g, arities):
@@ -50,7 +63,7 @@ def _max_q(g, arities):
 def test_numpy_definition_against_gammaln_restatement(case):
     x, mask, r, eta = make_case(case)
     n = 0
-    for name, g in zip(GRAPHS, make_graphs(case)):
+    for name, g in zip(graph_names(case), make_graphs(case)):
         if _max_q(g, r) > 10 ** 4:   # (the restatement enumerates all q configurations)
             continue
         got, want = bdeu_log_marginal_numpy(g, x, r, mask, eta), restated(g, x, r, mask, eta)
@@ -92,15 +105,36 @@ def test_score_equivalence_collider_and_limits():
     assert per[1] == 0.0 and per[0] == bdeu_log_marginal_numpy(G((0, 1), (1, 2)), x, r, per_node=True)[0] and per[2] < 0
 
 
-def test_bdeu_score_header_against_plain_loops():
-    src = os.path.join(ROOT, "tests", "tools", "bdeu_score_check.cpp")
+@pytest.fixture(scope="module")
+def score_check():
     with tempfile.TemporaryDirectory() as td:
-        exe = os.path.join(td, "bdeu_score_check")
-        subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", src, "-o", exe], check=True)
-        r = subprocess.run([exe], capture_output=True, text=True)
+        yield build_score_check(td)
+
+
+def test_bdeu_score_header_against_plain_loops(score_check):
+    r = subprocess.run([score_check], capture_output=True, text=True)
     print(r.stdout, r.stderr)
     assert r.returncode == 0, r.stderr
-    assert "bdeu_score_check: ok" in r.stdout
+    assert "bdeu_score_check: ok" in r.stdout and "check_hash: at most" in r.stdout
+
+
+def test_cases_cover_every_launch_shape_of_the_plan(score_check):
+    """the cases of tests/bdeu_states.py reach all six (waves per block, rows in LDS) pairs of bdeu_plan and every table size it can return
+    up to the limit; the plan is asked of the header (bdeu_score_check --plan), so a later change to it that un-covers a shape fails here"""
+    assert key_words([16] * 128) == 8 and key_words([16] * 40) == 3 and key_words([2] * 130) == 3 and key_words([4] * 30) == 1
+    plans = {case: plan_of(score_check, c["N"], key_words(arities_of(case))) for case, c in CASES.items()}
+    for case, pl in plans.items():
+        print(f"{case}: N = {CASES[case]['N']}, KW = {key_words(arities_of(case))}: waves {pl[0]}, rows in LDS {pl[1]}, T {pl[2]}, {pl[3]} bytes")
+    pairs = sorted({pl[:2] for pl in plans.values()})
+    sizes = sorted({pl[2] for pl in plans.values()})
+    print("plans", pairs, "table sizes", sizes)
+    assert pairs == [(w, l) for w in (1, 2, 4) for l in (0, 1)]
+    assert sizes == [64 << k for k in range(8)] and sizes[-1] == plan_of(score_check, 4096, 1)[2]
+    for N, tier in PLAN_TIERS.items():                                # what the table of cases says of itself
+        assert plans[f"d5_n{N}"][:3] == tier, (N, plans[f"d5_n{N}"], tier)
+    assert len(TIER_CASES) == len(PLAN_TIERS)
+    assert plans["d128_arity16_kw8"][:2] == (4, 0) and plans["d40_arity16_n1400"][:2] == (2, 0)
+    assert subprocess.run([score_check, "--plan", "4097", "1"], capture_output=True).returncode != 0
 
 
 def _model(d=5, arities=3, n=20, **kw):

@@ -1,22 +1,24 @@
 """BDeu on the device (include/dibs_hip.h, BDEU): k_bdeu_nodes against the float64 numpy definition on the
-constructed cases of tests/bdeu_states.py, one SVGD step stage by stage, determinism and chunking, the facade, two rank engines, and the
-refusals that need an engine.
+constructed cases of tests/bdeu_states.py (every launch shape of bdeu_plan among them; repeated graphs bit for bit), a second and later
+problem per wave at the largest and the smallest tables, one SVGD step stage by stage, determinism and chunking, the facade, two rank
+engines, and the refusals that need an engine.
 
 Bounds.  Node scores and per-graph sums are double on the device: 1e-9 (1 + |value|), the bound tests/test_gpu_f64.py holds double
 node scores to.  dibs_score_graphs' own `out` is float: it is held to the float rounding of the double sum (2^-23 relative, doubled).
 LOGPROBS_Z (float sums of the node scores) likewise; W_LIK to the 2e-3 of tests/test_gpu_parity.py."""
 import functools
+import tempfile
 
 import numpy as np
 import pytest
 
-from bdeu_states import CASES, GRAPHS, decode_masks, make_case, make_graphs
+from bdeu_states import CASES, TIER_CASES, build_score_check, decode_masks, graph_names, key_words, make_case, make_graphs, plan_of
 from conftest import assert_update_parity, make_data, rel_err, update_check
 from dibs_amd import random
 from dibs_amd._abi import make_config
 from dibs_amd._lib import DibsHipError
 from dibs_amd.engine import Engine
-from dibs_amd.inference import MarginalDiBS
+from dibs_amd.inference import MarginalDiBS, scoring
 from dibs_amd.inference.scoring import score_graphs
 from dibs_amd.models import BDeu, ErdosReniDAGDistribution, bdeu_log_marginal_numpy
 from dibs_amd.target import make_discrete_model
@@ -40,27 +42,51 @@ def _reference(case):
     return out
 
 
+@pytest.fixture(scope="module")
+def score_check():
+    """tests/tools/bdeu_score_check, for its --plan query: the launch shape of a size, from the header the launcher uses"""
+    with tempfile.TemporaryDirectory() as td:
+        yield build_score_check(td)
+
+
+def _resident_waves(score_check, N, KW):
+    """the waves bdeu_launch_nodes keeps resident: min(32, waves * floor(160 KiB / lds)) per CU"""
+    import torch
+    waves, _, _, lds = plan_of(score_check, N, KW)
+    return min(32, waves * ((160 * 1024) // lds)) * torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def _score(eng, g, x, mask):
+    """dibs_score_graphs of the n <= S graphs g: (node scores [n, d] double, the chunk's parent masks, out [n] float)"""
+    n, d = g.shape[0], g.shape[-1]
+    g = np.ascontiguousarray(g, np.int32)
+    out = np.empty(n, np.float32)
+    p = lambda a: None if a is None else a.ctypes.data
+    m32 = None if mask is None else np.ascontiguousarray(mask, np.int32)
+    rc = eng.lib.dibs_score_graphs(eng._h, p(g), None, n, p(x), p(m32), x.shape[0], p(out))
+    assert rc == 0, eng.lib.dibs_last_error()
+    ns = eng.read("NODE_SCORES")[:d * n].reshape(d, n).T              # the chunk's per-node doubles, [graph, node]
+    return ns.copy(), eng.read("PARENT_MASKS")[:d * n * ((d + 63) // 64)], out
+
+
 # ---- 1: hard graphs through dibs_score_graphs ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", list(CASES))
 def test_score_graphs_against_the_numpy_definition(case):
     x, mask, r, eta = make_case(case)
     g = make_graphs(case)
-    d, n = CASES[case]["d"], len(GRAPHS)
+    names = graph_names(case)
+    d, n = CASES[case]["d"], len(names)
     ref = _reference(case)
     eng = Engine(make_config(n_vars=d, n_particles=1, n_observations=1, likelihood="bdeu", bdeu_ess=eta, graph_prior="uniform",
                              n_grad_mc_samples=8, n_acyclicity_mc_samples=4))
     try:
         eng.set_arities(r)
-        out = np.empty(n, np.float32)
-        p = lambda a: None if a is None else a.ctypes.data
-        m32 = None if mask is None else np.ascontiguousarray(mask, np.int32)
-        rc = eng.lib.dibs_score_graphs(eng._h, p(g), None, n, p(x), p(m32), x.shape[0], p(out))
-        assert rc == 0, eng.lib.dibs_last_error()
-        ns = eng.read("NODE_SCORES")[:d * n].reshape(d, n).T          # the chunk's per-node doubles, [graph, node]
-        masks = eng.read("PARENT_MASKS")[:d * n * ((d + 63) // 64)]
+        ns, masks, out = _score(eng, g, x, mask)
+        if case in TIER_CASES:                                        # the same graphs twice in one call
+            ns8, masks8, _ = _score(eng, np.concatenate([g, g]), x, mask)
     finally:
         eng.close()
-    for i, name in enumerate(GRAPHS):
+    for i, name in enumerate(names):
         print(f"{case}/{name}: device {ns[i].sum():.12f} numpy {ref[i].sum():.12f} max node err "
               f"{np.abs(ns[i] - ref[i]).max():.2e}")
     assert np.array_equal(decode_masks(masks, 1, d, n)[0], g)
@@ -69,6 +95,31 @@ def test_score_graphs_against_the_numpy_definition(case):
     assert close(out, ns.sum(axis=1), F32), case                      # the float output is the rounded double sum
     if CASES[case]["interv"] == "node_all":
         assert (ns == 0.0).all(axis=0).any()                          # the node without a used row scores exactly 0, whatever its parents
+    if case in TIER_CASES:
+        assert np.array_equal(decode_masks(masks8, 1, d, 2 * n)[0], np.concatenate([g, g]))
+        assert np.array_equal(ns8[:n], ns8[n:]) and np.array_equal(ns8[:n], ns), case   # a repeated graph scores the same, bit for bit
+        assert close(ns8, np.concatenate([ref, ref])), case
+
+
+def test_second_pass_of_the_grid_at_large_n(score_check):
+    """256 graphs (16 distinct ones, tiled) against 2 049 rows through the facade: d S problems per chunk on the one resident wave per CU
+    of the (1 wave, rows in LDS) plan, so every wave scores at least two problems -- the key-mask clear, the table re-initialisation and
+    the stale entries of the previous problem's table"""
+    case = "d5_n2049"
+    x, mask, r, eta = make_case(case)
+    d, N = CASES[case]["d"], CASES[case]["N"]
+    rng = np.random.default_rng(11)
+    g16 = (rng.random((16, d, d)) < 0.5).astype(np.int32) * (1 - np.eye(d, dtype=np.int32))
+    assert len({gi.tobytes() for gi in g16}) == 16
+    got = score_graphs(BDeu(n_vars=d, arities=r, equivalent_sample_size=eta), np.tile(g16, (16, 1, 1)), None, x, mask)
+    S_chunk = int(next(reversed(scoring._ENGINES.values())).cfg.n_grad_mc_samples)
+    resident = _resident_waves(score_check, N, key_words(r))
+    print(f"{d * S_chunk} problems per call on {resident} resident waves")
+    assert d * S_chunk >= 2 * resident, (d, S_chunk, resident)        # (otherwise no wave strides: the test would show nothing)
+    want = np.array([bdeu_log_marginal_numpy(gi, x, r, mask, eta) for gi in g16])
+    got = got.reshape(16, 16)                                         # [copy, graph]
+    assert np.array_equal(got, np.tile(got[:1], (16, 1)))             # every copy of a graph, bit for bit
+    assert close(got[0], want), np.abs(got[0] - want).max()
 
 
 def test_score_graphs_facade_chunks_and_cache():
@@ -99,7 +150,7 @@ def _step_case(d, N, M=3, S=8):
     return x.astype(np.float32), mask, r, kw
 
 
-@pytest.mark.parametrize("d,N", [(8, 65), (70, 40)])
+@pytest.mark.parametrize("d,N", [(8, 65), (70, 40), (8, 2049)])
 def test_one_step_stage_by_stage(d, N):
     x, mask, r, kw = _step_case(d, N)
     M, S, t = kw["n_particles"], kw["n_grad_mc_samples"], 2
@@ -146,6 +197,46 @@ def test_one_step_stage_by_stage(d, N):
         bge.close()
 
 
+def test_second_pass_of_the_grid_at_small_n():
+    """one SVGD step with more problems than waves fit the device (32 per CU at the smallest tables): M d S > 32 CUs, so waves score a
+    second problem on training data, 8 rows with interventions on one column"""
+    import torch
+    d, S, N = 16, 32, 8
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    M = (32 * cus) // (d * S) + 4
+    assert M * d * S > 32 * cus
+    x, _, r, kw = _step_case(d, N, M=M, S=S)
+    mask = np.zeros((N, d), np.int32)
+    mask[[1, 5], 2] = 1
+    eng = _engine(x, mask, r, kw, key=3)
+    try:
+        eng.run(0, 1)
+        eng.run(2, 1)
+        g = decode_masks(eng.read("PARENT_MASKS"), M, d, S)           # [M, S, d, d]
+        ns = eng.read("NODE_SCORES").reshape(M, d, S)
+    finally:
+        eng.close()
+
+    @functools.lru_cache(maxsize=None)
+    def node_score(j, parents):
+        """score of node j under the parent set `parents` (bytes of a 0/1 column): the definition on the columns (parents, j) alone, the
+        parents' own scores left out by marking their rows unused"""
+        pa = np.nonzero(np.frombuffer(parents, np.int32))[0]
+        cols = list(pa) + [j]
+        gs = np.zeros((len(cols), len(cols)), np.int32)
+        gs[:-1, -1] = 1
+        ms = np.ones((N, len(cols)), np.int32)
+        ms[:, -1] = mask[:, j]
+        return bdeu_log_marginal_numpy(gs, x[:, cols], r[cols], ms, per_node=True)[-1]
+
+    want = np.array([[[node_score(j, np.ascontiguousarray(g[m, s, :, j]).tobytes()) for s in range(S)] for j in range(d)] for m in range(M)])
+    print(f"{M * d * S} problems on {cus} CUs, {node_score.cache_info().currsize} distinct (node, parent set); max err {np.abs(ns - want).max():.2e}")
+    full = bdeu_log_marginal_numpy(g[0, 0], x, r, mask, per_node=True)   # (the cached form is the definition's: one graph scored whole)
+    assert np.array_equal(full, want[0, :, 0])
+    assert g.sum() > 0 and np.abs(ns).max() > 0
+    assert close(ns, want), np.abs(ns - want).max()
+
+
 # ---- 3: determinism and chunking -----------------------------------------------------------------------------------------------------------
 def _engine(x, mask, r, kw, key=1, **more):
     e = Engine(make_config(likelihood="bdeu", **{**kw, **more}))
@@ -153,6 +244,24 @@ def _engine(x, mask, r, kw, key=1, **more):
     e.set_data(x, mask)
     e.init_particles(random.PRNGKey(key))
     return e
+
+
+@pytest.mark.parametrize("N", [220, 2049])
+def test_determinism_across_plans(N):
+    """three steps in one call and one by one, at (2 waves, rows global) and (1 wave, rows in LDS): state and node scores bit for bit"""
+    x, mask, r, kw = _step_case(8, N)
+    a, b = (_engine(x, mask, r, kw) for _ in range(2))
+    try:
+        a.run(0, 3)
+        for t in range(3):
+            b.run(t, 1)
+        sa, sb = a.get_state(), b.get_state()
+        for name in ("z", "v_z", "key", "baseline"):
+            assert np.array_equal(sa[name], sb[name]), name
+        assert np.array_equal(a.read("NODE_SCORES"), b.read("NODE_SCORES")) and np.abs(a.read("NODE_SCORES")).max() > 0
+    finally:
+        a.close()
+        b.close()
 
 
 def test_determinism_and_chunking():

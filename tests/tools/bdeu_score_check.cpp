@@ -1,12 +1,16 @@
 // CPU check of dibs_amd/csrc/bdeu_score.h (the arithmetic k_bdeu_nodes and the host packing share) against straightforward loops:
 //   rise and its terms against lgamma and against the sequential definition; log q against a plain sum; the field layout (no field
 //   straddles a word, fields disjoint, codes round-trip) and the key-mask compare against a tuple compare of the parents' codes, for
-//   arities 2, 3, 5, 16 and a layout of more than one word; the LDS plan's invariants for every N up to the limit.
+//   arities 2, 3, 5, 16 and a layout of more than one word; the LDS plan's invariants for every N up to the limit; the table hash
+//   (bdeu_mix, bdeu_slot) by the probes a sequential open-addressing table needs for distinct keys wherever their field sits in a word.
 // Built and run by tests/test_bdeu_host.py:  g++ -std=c++17 -Wall -Werror bdeu_score_check.cpp
+//   bdeu_score_check            every check; prints "bdeu_score_check: ok"
+//   bdeu_score_check --plan N KW    prints `waves rows_lds T lds_bytes` of bdeu_plan(N, KW) and checks nothing (exit 2: no plan)
 #include "../../dibs_amd/csrc/bdeu_score.h"
 
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include <vector>
 
 static int g_fail = 0;
@@ -119,7 +123,62 @@ static void check_plan() {
   CHECK(bdeu_plan(BDEU_MAX_N, BDEU_MAX_KW, &pl), "the largest size");
 }
 
-int main() {
+// N distinct keys of a 12-bit field at `shift`, inserted one after the other into an open-addressing table of T = bdeu_table_slots(N)
+// slots with the header's own mix and slot and the kernel's step (slot + 1) & (T - 1); `lead` != 0: a first key word, the same in every
+// row, mixed before.  Returns the slots visited in total.  Uniform hashing at load <= 1/2 visits at most 2.5 per insertion in expectation;
+// a slot function that does not see the field's bits visits about N / 2.
+static uint64_t hash_probes(int N, int shift, uint64_t lead, bool scattered) {
+  const uint32_t T = bdeu_table_slots(N);
+  std::vector<uint64_t> key(T, ~0ull);  // (no 12-bit field fills a word: ~0 is no key)
+  uint64_t probes = 0;
+  // distinct field values: 0 .. N - 1 themselves, or scattered -- an odd multiplier permutes 0 .. 4095
+  for (int n = 0; n < N; ++n) {
+    const uint64_t v = (uint64_t)(scattered ? ((uint32_t)n * 2741u + 977u) & 4095u : (uint32_t)n) << shift;
+    uint64_t h = 0;
+    if (lead) h = bdeu_mix(h, lead);
+    h = bdeu_mix(h, v);
+    uint32_t slot = bdeu_slot(h, T);
+    CHECK(slot < T, "slot %u outside a table of %u", slot, T);
+    for (;;) {
+      ++probes;
+      if (key[slot] == ~0ull) {
+        key[slot] = v;
+        break;
+      }
+      CHECK(key[slot] != v, "keys must be distinct");
+      slot = (slot + 1u) & (T - 1u);
+    }
+  }
+  return probes;
+}
+
+static void check_hash() {
+  const int Ns[] = {64, 1024, 4096};
+  const uint64_t leads[] = {0ull, 0x0000A5C3000F1E2Dull};
+  uint64_t worst_num = 0, worst_den = 1;
+  for (int N : Ns)
+    for (int shift = 0; shift <= 52; shift += 4)
+      for (uint64_t lead : leads)
+        for (int scattered = 0; scattered < 2; ++scattered) {
+          const uint64_t probes = hash_probes(N, shift, lead, scattered != 0);
+          CHECK(probes <= 4ull * (uint64_t)N, "hash: N = %d, %s 12-bit keys at shift %d%s: %llu probes for %d insertions (more than 4 N)", N,
+                scattered ? "scattered" : "consecutive", shift, lead ? " behind another word" : "", (unsigned long long)probes, N);
+          if (probes * worst_den > worst_num * (uint64_t)N) worst_num = probes, worst_den = (uint64_t)N;
+        }
+  printf("check_hash: at most %.2f probes per insertion\n", (double)worst_num / (double)worst_den);
+}
+
+int main(int argc, char** argv) {
+  if (argc == 4 && !strcmp(argv[1], "--plan")) {
+    BdeuPlan pl;
+    if (!bdeu_plan(atoi(argv[2]), atoi(argv[3]), &pl)) return 2;
+    printf("%d %d %u %zu\n", pl.waves, pl.rows_lds, pl.T, pl.lds_bytes);
+    return 0;
+  }
+  if (argc != 1) {
+    fprintf(stderr, "usage: bdeu_score_check [--plan N KW]\n");
+    return 2;
+  }
   check_rise();
   check_layout({2, 3, 5, 16}, 1);
   check_layout({2, 3, 4, 2, 5, 7, 8, 16, 3}, 1);
@@ -131,6 +190,7 @@ int main() {
     check_layout(ar, 3);
   }
   check_plan();
+  check_hash();
   if (g_fail) {
     fprintf(stderr, "bdeu_score_check: %d failures\n", g_fail);
     return 1;
